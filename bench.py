@@ -12,12 +12,17 @@ RCCL all-reduce of the counters, then the norms).  With N GPUs the same
 500M-pair stream is user-hash sharded over the ranks (strong scaling: the
 job is fixed, as config 3 states it).
 
-Beside it in the same line: config 4 (all-pairs top-100 of every item on the
-headline's table, cosines/s), config 5 (streaming batches + periodic
-refresh on that table), config 2 (100K items, weak scaling) as a secondary
-ingest line, config 1 (ML-100K shape), and the CPU baselines.
+A plain run does only what the headline needs: it builds the stream, warms
+up, times the K steps, writes its outputs when --dump-outputs is given, and
+prints the result line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+With --full, beside it in the same line: the per-phase breakdown of a step
+(extra steps with every phase scope event-timed), config 4 (all-pairs top-100
+of every item on the headline's table, cosines/s), config 5 (streaming batches
++ periodic refresh on that table), config 2 (100K items, weak scaling) as a
+secondary ingest line, config 1 (ML-100K shape), and the CPU baselines.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -45,11 +50,17 @@ def progress(msg):
     print(f"bench-progress: {time.time() - _T0:7.1f} s {msg}", file=sys.stderr, flush=True)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps of the headline")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the per-phase breakdown, configs 4, 5, 2 and 1 "
+                         "and the CPU baselines (the --no-* options below narrow this)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed (a fixed, seeded sample of the "
+                         "finished table: counters and similarities) as DIR/<name>.npy")
     # headline: config 3's shape (the metric's "@1M items")
     ap.add_argument("--n-items", type=int, default=1_000_000)
     ap.add_argument("--n-users", type=int, default=10_000_000)
@@ -71,7 +82,7 @@ def parse():
                     help="config 5: batches between periodic top-k refreshes (cms_top_k_refresh)")
     ap.add_argument("--stream-refresh-multi", action="store_true",
                     help="also run the config-5 streaming phase with a communicator (delta all-gather)")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 def visible_gpu_count(env=None, kfd_nodes="/sys/class/kfd/kfd/topology/nodes"):
@@ -662,11 +673,13 @@ def build_roofline(table, local_pairs, build_ms, build_n, pmc_kernel, pmc_file):
     return out
 
 
-def ingest_steps(table, items, users, npairs, steps, warmup, world, breakdown_names):
+def ingest_steps(table, items, users, npairs, steps, warmup, world, breakdown_names=None, after_timed=None):
     """`warmup` untimed then `steps` timed steps of reset + device COO ingest +
     finalize, bracketed by barrier + synchronize, max over ranks; HIP events
-    on the library's stream around k_build_rows only (timing level 1); then a
-    separate pass of <= 5 steps with every phase scope timed."""
+    on the library's stream around k_build_rows only (timing level 1).
+    `after_timed()` runs right after the timed region, with the table as the
+    last timed step left it.  With `breakdown_names` (--full) a separate pass
+    of <= 5 steps follows with every phase scope timed."""
     def step():
         table.reset()
         table.ingest_device_rows(items, users, None, npairs)
@@ -694,26 +707,66 @@ def ingest_steps(table, items, users, npairs, steps, warmup, world, breakdown_na
         elapsed = float(t.item())
     build_ms, build_n = table.timing("build_rows")
     ar_ms, ar_n = table.timing("allreduce")
-    table.set_timing(True, level=2)
-    table.reset_timing()
-    bsteps = max(1, min(steps, 5))
-    for _ in range(bsteps):
-        step()
-    table.synchronize()
-    breakdown = {}
-    for name in breakdown_names:
-        ms, n_ = table.timing(name)
-        if n_:
-            breakdown[name] = round(ms / bsteps, 4)
+    out = {"elapsed_s": elapsed, "ms_per_step": elapsed * 1e3 / steps, "build_ms": build_ms, "build_n": build_n,
+           "allreduce_ms_per_step": ar_ms / ar_n if ar_n else None}
+    if after_timed is not None:
+        table.set_timing(False)
+        after_timed()
+    if breakdown_names:
+        table.set_timing(True, level=2)
+        table.reset_timing()
+        bsteps = max(1, min(steps, 5))
+        for _ in range(bsteps):
+            step()
+        table.synchronize()
+        breakdown = {}
+        for name in breakdown_names:
+            ms, n_ = table.timing(name)
+            if n_:
+                breakdown[name] = round(ms / bsteps, 4)
+        out["breakdown_ms_per_step"] = breakdown
+        out["breakdown_source"] = f"{bsteps} extra steps after the timed region with every phase scope event-timed"
     table.set_timing(False)
     barrier()
-    return {"elapsed_s": elapsed, "ms_per_step": elapsed * 1e3 / steps, "build_ms": build_ms, "build_n": build_n,
-            "allreduce_ms_per_step": ar_ms / ar_n if ar_n else None, "breakdown_ms_per_step": breakdown,
-            "breakdown_source": f"{bsteps} extra steps after the timed region with every phase scope event-timed"}
+    return out
 
 
 BREAKDOWN = ["partition", "build_plan", "build_rows", "hot_norms", "reduce_hot", "norms", "merge_bounds", "merge_pack",
              "allreduce", "merge_unpack"]
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(table, items, outdir, seed=20261019):
+    """--dump-outputs: what the last timed step computed, as a caller of the
+    finished table reads it, written as outdir/<name>.npy (float64).  The
+    table itself is far larger than DUMP_LIMIT_BYTES, so a fixed, seeded
+    sample is written: the counters of the stream's 8 most frequent owners
+    (the u32 / multi-limb rows) and of random owners (cms_read_counters), and
+    the similarities of the frequent and of random query owners against a
+    random candidate set (cms_similarities: counters and norms of every owner
+    named).  The stream is seeded, so two builds write comparable files."""
+    n, d, w = table.num_owners, table.depth, table.width
+    rng = np.random.Generator(np.random.PCG64(seed))
+    counts = torch.bincount(items, minlength=n).cpu().numpy()
+    hot = np.argsort(-counts, kind="stable")[:min(8, n)]  # ties broken by owner row: the same rows every run
+    n_rows = int(min(n, max(hot.size, min(96, 32_000_000 // (d * w * 8)))))
+    rows = np.unique(np.concatenate([hot, rng.choice(n, n_rows - hot.size, replace=False)])).astype(np.int64)
+    counters = np.concatenate([table.read_counters(int(r), 1) for r in rows])
+    queries = np.unique(np.concatenate([hot, rng.choice(n, min(n, 32) - hot.size, replace=False)])).astype(np.int64)
+    cands = np.sort(rng.choice(n, min(n, 32768), replace=False)).astype(np.int64)
+    sims = np.stack([table.similarities(int(q), cands) for q in queries])
+    arrays = {"counter_rows": rows.astype(np.float64), "counters": counters,
+              "similarity_queries": queries.astype(np.float64), "similarity_candidates": cands.astype(np.float64),
+              "similarities": sims}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the limit of {DUMP_LIMIT_BYTES}")
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, np.float64))
+    return {"dir": outdir, "bytes": total, "arrays": {k: list(a.shape) for k, a in arrays.items()}}
 
 
 def csr_prefix_on_device(items, users, n_owners):
@@ -1177,15 +1230,24 @@ def config2_line(args, rank, world, local, device):
     return out
 
 
-def main():
-    args = parse()
+def main(argv=None):
+    args = parse(argv)
+    if args.no_headline and not args.full:
+        print("bench: --no-headline runs the secondary lines only, which a plain run leaves out: add --full",
+              file=sys.stderr)
+        sys.exit(2)
+    if not args.full:
+        # a plain run is the headline alone: set up, warm up, time the steps,
+        # dump the outputs when asked, print the line
+        args.no_cpu_baseline = args.no_extras = args.no_config1 = args.no_config2 = args.no_cosine_1m = True
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # self-launch: one rank per GPU; this parent never initialises HIP
         have = visible_gpu_count()
         if have < args.gpus:
             print(f"bench: --gpus {args.gpus} but only {have} GPU(s) visible", file=sys.stderr)
             sys.exit(2)
-        sys.exit(spawn_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]))
+        sys.exit(spawn_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)]
+                             + (sys.argv[1:] if argv is None else list(argv))))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1212,11 +1274,13 @@ def main():
         return float(v.item())
 
     # secondary lines first (their tables are freed before the 82 GB headline table)
-    progress("config 2 line")
-    config2 = None if args.no_config2 else config2_line(args, rank, world, local, device)
+    config2 = None
+    if not args.no_config2:
+        progress("config 2 line")
+        config2 = config2_line(args, rank, world, local, device)
     cfg1 = None
-    progress("config 1")
     if rank == 0 and world == 1 and not args.no_config1 and not args.no_extras:
+        progress("config 1")
         cfg1 = config1()
 
     if args.no_headline:
@@ -1239,7 +1303,17 @@ def main():
     items, users = config3_shard(n, args.n_users, args.pairs, rank, world, device)
     npairs = int(items.numel())
     torch.cuda.synchronize()
-    m = ingest_steps(table, items, users, npairs, args.steps, args.warmup, world, BREAKDOWN)
+    dumped = {}
+
+    def after_timed():
+        # the table is as the last timed step left it (the --full breakdown
+        # steps come later); rank 0 writes, the table is the same on every rank
+        if args.dump_outputs and rank == 0:
+            progress("writing the outputs of the last timed step")
+            dumped.update(dump_outputs(table, items, args.dump_outputs))
+
+    m = ingest_steps(table, items, users, npairs, args.steps, args.warmup, world,
+                     BREAKDOWN if args.full else None, after_timed)
     value = args.pairs * args.steps / m["elapsed_s"]  # the whole stream per step, over all ranks
     roof = build_roofline(table, npairs, m["build_ms"], m["build_n"], BUILD_KERNELS, "pmc_summary.json")
     st = table.stats()
@@ -1276,17 +1350,21 @@ def main():
                           "frac": step_bytes / (m["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBPS,
                           "u32_priced_bytes_per_gpu": u32_step_bytes,
                           "u32_priced_GBps": u32_step_bytes / (m["ms_per_step"] * 1e-3) / 1e9},
-        "breakdown_ms_per_step": m["breakdown_ms_per_step"],
-        "breakdown_source": m["breakdown_source"],
         "allreduce_ms_per_step": m["allreduce_ms_per_step"],
         "table": {"stored_bytes": stored, "hot_rows": int(st["hot_rows"]), "u32_bytes": n * d * w * 4},
     }
+    if "breakdown_ms_per_step" in m:  # --full
+        result["breakdown_ms_per_step"] = m["breakdown_ms_per_step"]
+        result["breakdown_source"] = m["breakdown_source"]
+    if dumped:
+        result["dumped_outputs"] = dumped
     if world > 1:
         mw = st["merge_words"]
         result["merge"] = {"allreduce_bytes_per_step": mw * 8, "u32_table_bytes": n * d * w * 4,
                            "payload_ratio": mw * 8 / (n * d * w * 4)}
-    progress("headline done; CPU baseline")
+    progress("headline done")
     if rank == 0 and not args.no_cpu_baseline:
+        progress("CPU baseline")
         # bounded sample of the same workload: the owners [0, 65536) of rank 0's
         # shard (IDs are a seeded permutation of popularity ranks, so an ID
         # prefix is a popularity-unbiased sample)
@@ -1308,8 +1386,8 @@ def main():
         cos_cpu = cosine_cpu_baseline(items, users, n, d, w)
     del items, users
     torch.cuda.empty_cache()
-    progress("config 4 / 5")
     if not args.no_cosine_1m:
+        progress("config 4 / 5")
         try:
             table.release_scratch()
             cos = cosine_1m(args, table, local, device, rank, world, bar, max_over_ranks)
@@ -1360,7 +1438,7 @@ COMPACT_LIMIT = 7000  # the driver's stdout tail window is ~8 KB; the line must 
 _COMPACT_TOP = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "step_roofline", "breakdown_ms_per_step",
                 "allreduce_ms_per_step", "table", "vs_cpu_baseline", "memory", "merge", "cosines_per_s",
-                "cosine_wall_s", "cosine_first_job_s", "cosine_roofline")
+                "cosine_wall_s", "cosine_first_job_s", "cosine_roofline", "dumped_outputs")
 
 
 def compact_line(res):

@@ -10,7 +10,7 @@ OUT=gpurun_out/kt${lib:+_$(basename $lib .so)}
 mkdir -p $OUT
 echo "== lib ${lib:-default}"
 MAHOUT_CMS_LIB=$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT -o run --output-format csv -- \
-    python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --no-cosine-1m ${BENCH_ARGS} \
+    python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras --no-cosine-1m ${BENCH_ARGS} \
     > $OUT/bench.json 2> $OUT/trace.log \
   && OUT=$OUT python3 - <<'P' || exit 1
 import csv, glob

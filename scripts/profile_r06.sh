@@ -17,8 +17,8 @@ OUT=gpurun_out/prof_$MODE
 rm -rf $OUT
 mkdir -p $OUT
 case $MODE in
-  ingest|ingest_sq) CMD="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --no-config1 --no-config2 --no-cosine-1m" ;;
-  config2) CMD="python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras --no-config1 --no-headline" ;;
+  ingest|ingest_sq) CMD="python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras --no-config1 --no-config2 --no-cosine-1m" ;;
+  config2) CMD="python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras --no-config1 --no-headline" ;;
   cosine)  CMD="python3 scripts/cos_job_probe.py ${COS_ARGS:-1000000 500000000 8192 100}" ;;
   *) echo "mode?"; exit 2 ;;
 esac

@@ -5,6 +5,7 @@
 # or time limit ends the script.
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
+BENCH_OUT=${BENCH_OUT:-bench_out}; mkdir -p "$BENCH_OUT"  # the full bench's line and log
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 timeout -k 10 900 python -u -m pytest tests -m gpu -v -p no:cacheprovider --timeout 300 --timeout-method thread \
@@ -15,9 +16,9 @@ grep -E "^(FAILED|ERROR)" gpurun_out/pytest_gpu.log | head -20
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest ended with status $rc: stopping"; exit $rc; fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || { echo "smoke failed"; tail -5 gpurun_out/smoke.log; exit 1; }
 echo "smoke ok"
-timeout -k 10 700 python bench.py --steps 10 --warmup 3 > gpurun_out/bench.json 2> gpurun_out/bench.err \
-  || { echo "bench failed"; tail -20 gpurun_out/bench.err; exit 1; }
+timeout -k 10 700 python bench.py --full --steps 10 --warmup 3 > $BENCH_OUT/bench.json 2> $BENCH_OUT/bench.err \
+  || { echo "bench failed"; tail -20 $BENCH_OUT/bench.err; exit 1; }
 echo "bench ok"
-python -c "import json; print(json.dumps(json.load(open('gpurun_out/bench.json'))['summary']))"
+python -c "import json; print(json.dumps(json.load(open('$BENCH_OUT/bench.json'))['summary']))"
 [ "${SKIP_COS_PROF:-0}" = 1 ] || bash scripts/profile_r04.sh cosine || exit 1
 exit $rc

@@ -5,6 +5,7 @@
 # time limit ends the script.
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
+BENCH_OUT=${BENCH_OUT:-bench_out}; mkdir -p "$BENCH_OUT"  # the full bench's line and log
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TESTS=${TESTS:-tests}
@@ -18,8 +19,8 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_ou
 echo "smoke ok"
 bash scripts/profile_r04.sh ingest_sq || exit 1
 bash scripts/profile_r04.sh ingest || exit 1
-timeout -k 10 700 python bench.py --steps 10 --warmup 3 > gpurun_out/bench.json 2> gpurun_out/bench.err \
-  || { echo "bench failed"; tail -20 gpurun_out/bench.err; exit 1; }
+timeout -k 10 700 python bench.py --full --steps 10 --warmup 3 > $BENCH_OUT/bench.json 2> $BENCH_OUT/bench.err \
+  || { echo "bench failed"; tail -20 $BENCH_OUT/bench.err; exit 1; }
 echo "bench ok"
-python -c "import json; print(json.dumps(json.load(open('gpurun_out/bench.json'))['summary']))"
+python -c "import json; print(json.dumps(json.load(open('$BENCH_OUT/bench.json'))['summary']))"
 exit $rc

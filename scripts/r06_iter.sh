@@ -12,6 +12,7 @@
 # the later steps run, any other non-zero status ends the script.
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
+BENCH_OUT=${BENCH_OUT:-bench_out}; mkdir -p "$BENCH_OUT"  # the full bench's line and log
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 STEPS=${STEPS:-"tests smoke ab"}
@@ -33,7 +34,7 @@ for step in $STEPS; do
     trace)
       rm -rf gpurun_out/prof_ingest
       timeout -k 10 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_ingest -o run --output-format csv -- \
-          python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --no-config1 --no-config2 --no-cosine-1m \
+          python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras --no-config1 --no-config2 --no-cosine-1m \
           > gpurun_out/prof_ingest.log 2>&1 || { echo "ingest trace failed"; exit 1; }
       python3 scripts/kstats.py gpurun_out/prof_ingest 30
       echo "ingest trace ok" ;;
@@ -46,7 +47,7 @@ for step in $STEPS; do
           env:*) IFS='+' read -r -a envs <<< "${arm#env:}"; tag=$(echo "${arm#env:}" | tr '=+/.' '____') ;;
           *) envs=(MAHOUT_CMS_LIB="$PWD/$arm"); tag=$(basename "$arm" .so) ;;
         esac
-        env "${envs[@]}" timeout -k 10 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras \
+        env "${envs[@]}" timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras \
             --no-config1 --no-config2 --no-cosine-1m > gpurun_out/ab_${tag}.json 2> gpurun_out/ab_${tag}.err \
           || { echo "A/B arm $tag failed"; tail -5 gpurun_out/ab_${tag}.err; exit 1; }
         python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[1], round(d['ms_per_step'],3), d.get('breakdown_ms_per_step'))" gpurun_out/ab_${tag}.json
@@ -64,7 +65,7 @@ for step in $STEPS; do
           *) envs=(MAHOUT_CMS_LIB="$PWD/$arm"); tag=$(basename "$arm" .so) ;;
         esac
         env "${envs[@]}" timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/kt/$tag -o run --output-format csv -- \
-            python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-config1 --no-config2 --no-cosine-1m \
+            python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-config1 --no-config2 --no-cosine-1m \
             > gpurun_out/kt_$tag.log 2>&1 || { echo "ktrace arm $tag failed"; tail -5 gpurun_out/kt_$tag.log; exit 1; }
       done
       python3 scripts/ktrace_table.py gpurun_out/kt ;;
@@ -75,10 +76,10 @@ for step in $STEPS; do
       bash scripts/profile_r06.sh cosine || exit 1
       python3 scripts/summarize_cos_pmc.py gpurun_out/prof_cosine r06 || exit 1 ;;
     bench)
-      timeout -k 10 700 python bench.py --steps 10 --warmup 3 --detail-out gpurun_out/bench_detail.json > gpurun_out/bench.json 2> gpurun_out/bench.err \
-        || { echo "bench failed"; tail -20 gpurun_out/bench.err; exit 1; }
+      timeout -k 10 700 python bench.py --full --steps 10 --warmup 3 --detail-out $BENCH_OUT/bench_detail.json > $BENCH_OUT/bench.json 2> $BENCH_OUT/bench.err \
+        || { echo "bench failed"; tail -20 $BENCH_OUT/bench.err; exit 1; }
       echo "bench ok"
-      python3 -c "import json; print(json.dumps(json.load(open('gpurun_out/bench.json'))['summary']))" ;;
+      python3 -c "import json; print(json.dumps(json.load(open('$BENCH_OUT/bench.json'))['summary']))" ;;
   esac
 done
 exit $rc
