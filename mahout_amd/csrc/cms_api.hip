@@ -341,16 +341,9 @@ static int create_impl(const cms_params* p, bool per_owner, cms_handle** out) {
     h->tune.list_keys = std::max(0, std::min(256, num("CMS_LIST_KEYS", h->tune.list_keys)));
     h->tune.mid_u4_keys = num("CMS_MID_U4_KEYS", h->tune.mid_u4_keys);
     h->tune.mid_u8_keys = num("CMS_MID_U8_KEYS", h->tune.mid_u8_keys);
-    h->tune.mid_u8_image = num("CMS_MID_U8_IMAGE", h->tune.mid_u8_image);
-    h->tune.nib_persist = num("CMS_NIB_PERSIST", h->tune.nib_persist);
-    h->tune.mid_image = num("CMS_MID_IMAGE", h->tune.mid_image);
     h->tune.build_streams = num("CMS_BUILD_STREAMS", h->tune.build_streams);
     h->tune.plan_side = num("CMS_PLAN_SIDE", h->tune.plan_side);
-    h->tune.slice_reduce = num("CMS_SLICE_REDUCE", h->tune.slice_reduce);
-    h->tune.mid_waves = num("CMS_MID_WAVES", h->tune.mid_waves);
     h->tune.split_keys = num("CMS_SPLIT_KEYS", h->tune.split_keys);
-    h->tune.mid_threads = num("CMS_MID_THREADS", h->tune.mid_threads);
-    h->tune.nib_rows_once = num("CMS_NIB_ROWS_ONCE", h->tune.nib_rows_once);
     h->tune.po_no_prune = num("CMS_PO_NO_PRUNE", h->tune.po_no_prune);
     h->tune.po_bound_rows = num("CMS_PO_BOUND_ROWS", h->tune.po_bound_rows);
     h->tune.po_bound_part2 = num("CMS_PO_BOUND_PART2", h->tune.po_bound_part2);
@@ -359,7 +352,6 @@ static int create_impl(const cms_params* p, bool per_owner, cms_handle** out) {
     h->tune.forms = !flag("CMS_NO_FORMS");
     h->tune.no_compact = flag("CMS_NO_COMPACT");
     h->tune.no_vmm = flag("CMS_NO_VMM");
-    h->tune.early_slices = flag("CMS_EARLY_SLICES") ? 1 : 0;
     h->tune.hot_routing = !flag("CMS_NO_HOT_ROUTING");
     h->tune.fp4 = !flag("CMS_NO_FP4");
     h->tune.mls = !flag("CMS_NO_MLS");
@@ -405,15 +397,9 @@ static int create_impl(const cms_params* p, bool per_owner, cms_handle** out) {
   if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamDefault)) != hipSuccess ||
       (e = hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking)) != hipSuccess ||
       (e = hipStreamCreateWithFlags(&h->side_stream2, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipStreamCreateWithFlags(&h->side_stream3, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&h->ev_p1, hipEventDisableTiming)) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&h->ev_e1, hipEventDisableTiming)) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&h->ev_early, hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&h->ev_join3, hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&h->ev_spans, hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&h->ev_plan, hipEventDisableTiming)) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming)) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&h->ev_fork2, hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&h->ev_join2, hipEventDisableTiming)) != hipSuccess ||
 #ifdef CMS_BUILD_GATHERHASH  // bound analysis only (cms_hash.h): the gathered table, contents unset
@@ -472,14 +458,9 @@ void cms_destroy(cms_handle* h) {
   if (h->order_ev) (void)hipEventDestroy(h->order_ev);
   if (h->side_stream) (void)hipStreamSynchronize(h->side_stream);
   if (h->side_stream2) (void)hipStreamSynchronize(h->side_stream2);
-  if (h->side_stream3) (void)hipStreamSynchronize(h->side_stream3);
-  for (hipEvent_t ev : {h->ev_p1, h->ev_e1, h->ev_early})
-    if (ev) (void)hipEventDestroy(ev);
   if (h->ev_join3) (void)hipEventDestroy(h->ev_join3);
   if (h->ev_spans) (void)hipEventDestroy(h->ev_spans);
   if (h->ev_plan) (void)hipEventDestroy(h->ev_plan);
-  if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-  if (h->ev_join) (void)hipEventDestroy(h->ev_join);
   if (h->ev_fork2) (void)hipEventDestroy(h->ev_fork2);
   if (h->ev_join2) (void)hipEventDestroy(h->ev_join2);
   free_query_pool(h);
@@ -490,7 +471,7 @@ void cms_destroy(cms_handle* h) {
     if (b) (void)hipFree(b);
   if (h->h_pin) (void)hipHostFree(h->h_pin);
   DevBuf* ws[] = {&h->ws_in_row, &h->ws_in_key, &h->ws_in_val, &h->ws_p1_row, &h->ws_p1_key, &h->ws_p1_val,
-                  &h->ws_csr_key, &h->ws_csr_val, &h->ws_csr_off, &h->ws_csr_hi, &h->ws_hotpart, &h->ws_hist, &h->ws_small, &h->ws_partials, &h->ws_slicepart,
+                  &h->ws_csr_key, &h->ws_csr_val, &h->ws_csr_off, &h->ws_csr_hi, &h->ws_hotpart, &h->ws_hist, &h->ws_small, &h->ws_partials,
                   &h->ws_hot, &h->ws_query, &h->ws_out, &h->ws_limb0, &h->ws_limbmeta, &h->ws_limbhot,
                   &h->ws_hotlist, &h->ws_tiles, &h->ws_slab, &h->ws_topq, &h->vl[0].buf, &h->vl[1].buf, &h->ws_nsq, &h->ws_cand,
                   &h->dlog_row, &h->dlog_key, &h->dlog_val, &h->dlog_cnt, &h->dlog_all, &h->ws_srow,
@@ -502,7 +483,6 @@ void cms_destroy(cms_handle* h) {
   if (h->stream) (void)hipStreamDestroy(h->stream);
   if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
   if (h->side_stream2) (void)hipStreamDestroy(h->side_stream2);
-  if (h->side_stream3) (void)hipStreamDestroy(h->side_stream3);
   delete h;
 }
 
@@ -809,7 +789,7 @@ int cms_release_scratch(cms_handle* h) {
   Guard g(h);
   CMS_HIP(hipStreamSynchronize(h->stream));
   DevBuf* ws[] = {&h->ws_in_row, &h->ws_in_key, &h->ws_in_val, &h->ws_p1_row, &h->ws_p1_key, &h->ws_p1_val,
-                  &h->ws_csr_key, &h->ws_csr_val, &h->ws_csr_off, &h->ws_csr_hi, &h->ws_hotpart, &h->ws_hist, &h->ws_hot, &h->ws_slicepart, &h->ws_query,
+                  &h->ws_csr_key, &h->ws_csr_val, &h->ws_csr_off, &h->ws_csr_hi, &h->ws_hotpart, &h->ws_hist, &h->ws_hot, &h->ws_query,
                   &h->ws_out, &h->ws_slab, &h->ws_topq, &h->ws_tiles, &h->ws_cand, &h->ws_srow,
                   &h->ws_mbnd, &h->ws_mbits, &h->ws_mwoff, &h->ws_mpacked, &h->rf_ids, &h->rf_sc, &h->rf_cnt,
                   &h->rf_full, &h->rf_touch, &h->rf_new, &h->rf_redo, &h->rf_perm};

@@ -241,22 +241,14 @@ struct Tunables {
   // attempts would only be thrown away (the escalation stays as the safety net)
   int mid_u4_keys = 768;    // CMS_MID_U4_KEYS: more keys start at u8 (list-row owners always try 4-bit)
   int mid_u8_keys = 12288;  // CMS_MID_U8_KEYS: more keys start at u16
-  int nib_persist = 0;      // CMS_NIB_PERSIST=1: k_build_nibbles as persistent waves (else one owner per wave)
   int plan_side = 1;        // CMS_PLAN_SIDE=0: the build plan after the whole partition on the handle's stream
   int build_streams = 3;    // CMS_BUILD_STREAMS=2: the mid class after the byte class on one side stream
-  int mid_image = 0;        // CMS_MID_IMAGE=1: mid owners through the one-pass u16 image (k_build_image; slower on MI355X)
   int po_dense_x4 = 4;      // CMS_PO_DENSE_X4: group kernel's dense dots when 4 w <= this x nnz(u1)
   int po_bound_part2 = 1;   // CMS_PO_BOUND_PART2=0: the widest narrow part through the group kernel, unbounded
   int po_bound_rows = 1;    // CMS_PO_BOUND_ROWS: sketch rows of the wide owners' upper bound (1 or 2)
   int po_no_prune = 0;      // CMS_PO_NO_PRUNE=1: every (query, wide owner) pair through k_po_pairs (no row-0 bound)
   int po_no_bigq = 0;       // CMS_PO_NO_BIGQ=1: per-owner all-pairs without k_po_bigq (every query in the group kernel)
-  int mid_u8_image = 0;     // CMS_MID_U8_IMAGE=1: mid owners starting at u8 count all sketch rows in one [d][w] u8 image
-  int nib_rows_once = 0;    // CMS_NIB_ROWS_ONCE=1: a byte-class wave hashes its first key slot's d rows up front (d = 4 or 5)
-  int mid_threads = 256;    // CMS_MID_THREADS=128: k_build_mid owners on 2-wave workgroups (twice as many in flight)
   int split_keys = 0;       // CMS_SPLIT_KEYS: rows with more keys get a u32 slot and k_build_slices (0: 8192, 16384 at w >= 8192)
-  int mid_waves = 0;        // CMS_MID_WAVES=<k>: mid owners one wave each (k_build_mid_waves), k persistent 4-wave workgroups per CU; 0: k_build_mid
-  int slice_reduce = 0;     // CMS_SLICE_REDUCE=1: split owners' slices leave u16 images summed by k_slice_reduce (no slot atomics)
-  int early_slices = 0;     // CMS_EARLY_SLICES=1: the hot-routed split owners are built beside pass 2 of the partition
   bool forms = true;       // CMS_NO_FORMS=1: every narrow row stays u16 (no 1/2/4/8-bit forms)
   bool no_compact = false; // CMS_NO_COMPACT=1: every narrow row keeps a whole u16 slot (no compact layout)
   bool no_vmm = false;     // CMS_NO_VMM=1: the compact arena as one hipMalloc grown by copying (no virtual range)
@@ -272,25 +264,16 @@ struct cms_handle {
   int device = 0;
   int num_cus = 256;  // compute units of the device (persistent grids)
   hipStream_t stream = nullptr;
-  // side stream of the row build: the hot owners' slices run beside the row
-  // kernels (ordered by ev_fork / ev_join on the handle's stream)
+  // side stream of the row build: the byte-class kernels run beside the slot
+  // rows (ordered by ev_fork2 / ev_join2 on the handle's stream), and the
+  // build plan beside a partition's last scatter (ev_spans / ev_plan)
   hipStream_t side_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;    // slices experiment (CMS_SLICES_SIDE)
   hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr;  // byte / mid class kernels beside the slot rows
   hipStream_t side_stream2 = nullptr;                 // the mid class beside the byte class (Tunables::build_streams 3)
   hipEvent_t ev_join3 = nullptr;
   // the owner spans of a partition are ready (recorded before its last
   // scatter): the build plan may start on the side stream meanwhile
   hipEvent_t ev_spans = nullptr, ev_plan = nullptr;
-  // early slices (Tunables::early_slices): pass 1 of the partition has placed
-  // the hot-routed owners' keys (ev_p1); their build runs on side_stream3,
-  // ev_e1 marks their rows claimed (hidx, early flags), ev_early its end
-  hipStream_t side_stream3 = nullptr;
-  hipEvent_t ev_p1 = nullptr, ev_e1 = nullptr, ev_early = nullptr;
-  bool p1_event = false;
-  const unsigned long long* p1_slotkey = nullptr;  // hot slot t -> owner row + 1 (0: free)
-  const uint32_t* p1_bs1 = nullptr;                // pass-1 bin starts: hot slot t spans [bs1[P1 + t], bs1[P1 + t + 1])
-  int p1_P1 = 0, p1_nslots = 0;
   bool spans_event = false, plan_side_request = false;
   bool plan_side_active = false;  // h->stream and h->side_stream are swapped (the build plan's section)
   // Writers (ingest, finalize, reset, top-k passes, ...) hold mu exclusively;
@@ -331,7 +314,6 @@ struct cms_handle {
   cms::DevBuf ws_bound, ws_force, ws_plist;  // promotion scratch: u64 [n], u8 [n], i32 [n] + count
   cms::DevBuf ws_blist;                      // row build: slot-row and mid-class row lists + counts
   cms::DevBuf ws_layout;                     // row layout: capacities / scan (u32 [2n + ...]); widen: movers
-  cms::DevBuf ws_early;                      // early slices: spans i64 [2n], flags u8 [n], HotInfo / slice map
   int64_t hot_cap = 0, hot_used = 0;
   cms::TableView tview() const {
     return cms::TableView{d_t16, hot_tab.as<uint32_t>(), d_hidx, dw, p.width, d_off};
@@ -401,7 +383,6 @@ struct cms_handle {
   cms::DevBuf ws_csr_key, ws_csr_val, ws_csr_off, ws_csr_hi;
   cms::DevBuf ws_hotpart;  // hot-owner routing of the partition: slot keys [1024] u64, sample counts [n] u32
   cms::DevBuf ws_hist, ws_small, ws_partials, ws_hot;
-  cms::DevBuf ws_slicepart;  // row build: u16 [mapped slices][d*w] slice images of split owners (k_slice_reduce)
   cms::DevBuf ws_query, ws_query2, ws_out, ws_srow, ws_f4, ws_i8blk;
   cms::DevBuf ws_limb0, ws_limbmeta, ws_limbhot, ws_hotlist, ws_tiles, ws_slab, ws_topq, ws_nsq, ws_cand;
 
@@ -516,9 +497,6 @@ int local_norms(cms_handle* h);
 // round trip: that many slots are reserved and claimed on the device).
 int promote_rows(cms_handle* h, const uint64_t* d_bound, const uint8_t* d_force, bool copy_old, int64_t max_new = -1,
                  uint64_t whole_bound = 0);
-// count consecutive hot slots for the caller's rows (host bookkeeping; the
-// table grows first if needed): [*base, *base + count)
-int reserve_hot_slots(cms_handle* h, int64_t count, int64_t* base);
 // rows holding a u32 slot (synchronises the stream)
 int count_hot_rows(cms_handle* h, int64_t* out);
 // rows per storage form: [0] hot, [1] u16, [2] u8, [3] nibble (synchronises)

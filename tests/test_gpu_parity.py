@@ -781,20 +781,44 @@ def test_multi_limb_slab_kernel_equals_reference_path(oracle):
             assert same(sc[q, :cnt[q]], esc), q
 
 
+# largest counter each narrow storage form holds (a list row's counters stay below 2^8)
+FORM_CAP = {"u16": 65535, "u8": 255, "u4": 15, "u2": 3, "u1": 1, "list": 255}
+
+
+def check_sampled_owners(oracle, t, sel, exp):
+    """The sampled owners `sel` of the finalized table `t` against their
+    oracle sketches `exp` ([sel][d][w]): the counters bit for bit; each
+    owner's storage form wide enough for its largest oracle counter, and its
+    reported bound no less where a bound is kept (the forms below u16); and
+    every sampled owner's similarities to the sampled owners equal to the
+    oracle's cosines of `exp`."""
+    got = t.read_counters_device().cpu().numpy()[sel].astype(np.float64)
+    assert same(got, exp)
+    form, bound = t.owner_forms()
+    for i, r in enumerate(sel.tolist()):
+        name, mx = SketchTable.FORMS[form[r]], exp[i].max()
+        if name == "u32":
+            continue
+        assert mx <= FORM_CAP[name], (r, name, mx)
+        if name != "u16":
+            assert mx <= bound[r] <= FORM_CAP[name], (r, name, mx, bound[r])
+    for i, q in enumerate(sel.tolist()):
+        ref = _oracle_row_sims(oracle, exp, i)
+        ref[i] = oracle.cosine_cm(exp[i], exp[i])
+        assert same(t.similarities(q, sel), ref), q
+
+
 @pytest.mark.parametrize("accumulate", [False, True])
-def test_slice_images_reduce_equals_slot_atomics(oracle, accumulate, monkeypatch):
-    """k_build_slices with CMS_SLICE_REDUCE=1 writes each 65535-key slice's
-    u16 image and k_slice_reduce sums them into the slot rows (stored whole,
-    norms and maxima derived in the same pass, for owners of <= 16 slices;
-    64-bit atomics plus k_hot_norms for the Zipf head's many-slice owners):
-    the table, the norms (through the similarities) and the row maxima equal
-    the slot-atomic path's bit for bit, in a fresh build and in an
-    accumulating one (a second bulk batch into the live table), and the
-    heaviest owners match the oracle."""
-    import torch
+def test_multi_slice_owners_match_oracle(oracle, accumulate):
+    """Split owners of 20, 5 and 2 slices of 65535 keys (k_build_slices adds
+    each slice's u16 image into the owner's u32 slot row, k_hot_norms derives
+    the norms and maxima) over a Zipf tail of narrow and mid rows, in a fresh
+    build and in an accumulating one (a second bulk batch into the live
+    table): the heaviest owners' counters, forms and similarities match the
+    oracle."""
     n, d, w = 4096, 5, 8192
     rng = np.random.Generator(np.random.PCG64(21))
-    # owner 0: 1.3M keys (20 slices: two groups), owner 1: 300K (5 slices),
+    # owner 0: 1.3M keys (20 slices), owner 1: 300K (5 slices),
     # owner 2: 70K (2 slices), owners 3..: a Zipf tail (narrow and mid rows)
     heavy = [np.zeros(1_300_000, np.int64), np.ones(300_000, np.int64), np.full(70_000, 2, np.int64)]
     tail_items, tail_users = zipf_stream(3_000_000, n - 3, 2_000_000, seed=8)
@@ -803,35 +827,24 @@ def test_slice_images_reduce_equals_slot_atomics(oracle, accumulate, monkeypatch
     perm = rng.permutation(items.size)
     items, users = items[perm], users[perm]
     half = items.size // 2
-    got = {}
-    for mode in ("atomics", "reduce"):
-        monkeypatch.setenv("CMS_SLICE_REDUCE", "1" if mode == "reduce" else "0")
-        with SketchTable(n, depth=d, width=w, seed=13) as t:
-            if accumulate:
-                t.ingest(items[:half], users[:half])
-                t.ingest(items[half:], users[half:])
-            else:
-                t.ingest(items, users)
-            t.finalize()
-            got[mode] = (t.read_counters_device().cpu(),
-                         np.stack([t.similarities(q, np.arange(n)) for q in (0, 1, 2, 3, 100)]),
-                         t.stats()["hot_rows"])
-            torch.cuda.synchronize()
-    assert torch.equal(got["atomics"][0], got["reduce"][0])
-    assert same(got["atomics"][1], got["reduce"][1])
-    assert got["reduce"][2] >= 3
     sel = np.array([0, 1, 2, 3])
     m = np.isin(items, sel)
     exp = oracle_table(oracle, sel.size, d, w, 13, items[m], users[m], None)
-    assert same(got["reduce"][0].numpy()[sel].astype(np.float64), exp)
+    with SketchTable(n, depth=d, width=w, seed=13) as t:
+        if accumulate:
+            t.ingest(items[:half], users[:half])
+            t.ingest(items[half:], users[half:])
+        else:
+            t.ingest(items, users)
+        t.finalize()
+        assert t.stats()["hot_rows"] >= 3
+        check_sampled_owners(oracle, t, sel, exp)
 
 
-def test_byte_class_rows_once_equal_row_by_row(oracle, monkeypatch):
-    """k_build_nibbles with CMS_NIB_ROWS_ONCE=1 (the first key slot's d
-    buckets hashed up front, d = 5) builds the same table and forms as the
-    row-by-row hashing, on a byte-class-heavy model (list rows, 1-/2-/4-bit
-    rows, k_build_bytes escalations, keys past 2^32)."""
-    import torch
+def test_byte_class_heavy_model_matches_oracle(oracle):
+    """A byte-class-heavy model at d = 5 (list rows, 1-/2-/4-bit rows of
+    k_build_nibbles, k_build_bytes escalations, keys past 2^32): sampled
+    owners' counters, forms and similarities match the oracle."""
     n, d, w = 30_000, 5, 8192
     rng = np.random.Generator(np.random.PCG64(41))
     sizes = rng.integers(1, 257, n)
@@ -840,37 +853,22 @@ def test_byte_class_rows_once_equal_row_by_row(oracle, monkeypatch):
     users[items % 97 == 0] += 1 << 33
     perm = rng.permutation(items.size)
     items, users = items[perm], users[perm]
-    got = {}
-    for mode in ("0", "1"):
-        monkeypatch.setenv("CMS_NIB_ROWS_ONCE", mode)
-        with SketchTable(n, depth=d, width=w, seed=19) as t:
-            t.ingest(items, users)
-            t.finalize()
-            got[mode] = (t.read_counters_device().cpu(), t.owner_forms(),
-                         np.stack([t.similarities(q, np.arange(n)) for q in (0, 97, 5000)]))
-            torch.cuda.synchronize()
-    assert torch.equal(got["0"][0], got["1"][0])
-    for a, b in zip(got["0"][1], got["1"][1]):
-        assert np.array_equal(np.asarray(a), np.asarray(b))
-    assert same(got["0"][2], got["1"][2])
     sel = np.array([0, 97, 5000, 29_999])
     m = np.isin(items, sel)
     remap = np.full(n, -1, np.int64)
     remap[sel] = np.arange(sel.size)
     exp = oracle_table(oracle, sel.size, d, w, 19, remap[items[m]], users[m], None)
-    assert same(got["1"][0].numpy()[sel].astype(np.float64), exp)
+    with SketchTable(n, depth=d, width=w, seed=19) as t:
+        t.ingest(items, users)
+        t.finalize()
+        check_sampled_owners(oracle, t, sel, exp)
 
 
-@pytest.mark.parametrize("variant", ["CMS_MID_WAVES=5", "CMS_MID_THREADS=128"])
-def test_mid_waves_equal_mid_workgroups(oracle, monkeypatch, variant):
-    """k_build_mid_waves (CMS_MID_WAVES: one wave per mid-class owner, 4-bit
-    then u8 rows, list rows for owners of <= 1024 keys; u16 owners and keys
-    >= 2^32 handed to k_build_mid) and k_build_mid on 128-thread workgroups
-    (CMS_MID_THREADS=128) build the same table, the same row forms and the
-    same norms as k_build_mid's 256-thread owners, and sampled mid owners
+def test_mid_class_owners_match_oracle(oracle):
+    """Mid-class owners (k_build_mid: 4-bit, u8 and u16 rows, list rows for
+    owners of <= 1024 keys, an owner whose keys reach past 2^32) over a
+    byte-class tail: sampled mid owners' counters, forms and similarities
     match the oracle."""
-    var, val = variant.split("=")
-    import torch
     n, d, w = 20_000, 5, 8192
     rng = np.random.Generator(np.random.PCG64(31))
     # mid owners of 300..14000 keys with Zipf users (repeats: u8 and u16 rows),
@@ -883,28 +881,15 @@ def test_mid_waves_equal_mid_workgroups(oracle, monkeypatch, variant):
     users[big] = users[big] + (1 << 33)
     perm = rng.permutation(items.size)
     items, users = items[perm], users[perm]
-    got = {}
-    for mode in ("workgroups", "waves"):
-        if mode == "waves":
-            monkeypatch.setenv(var, val)
-        else:
-            monkeypatch.delenv(var, raising=False)
-        with SketchTable(n, depth=d, width=w, seed=17) as t:
-            t.ingest(items, users)
-            t.finalize()
-            got[mode] = (t.read_counters_device().cpu(), t.owner_forms(),
-                         np.stack([t.similarities(q, np.arange(n)) for q in (0, 7, 4000, 9000)]))
-            torch.cuda.synchronize()
-    assert torch.equal(got["workgroups"][0], got["waves"][0])
-    for a, b in zip(got["workgroups"][1], got["waves"][1]):
-        assert np.array_equal(np.asarray(a), np.asarray(b))
-    assert same(got["workgroups"][2], got["waves"][2])
     sel = np.array([0, 7, 11, 3100, 4000])
     m = np.isin(items, sel)
     remap = np.full(n, -1, np.int64)
     remap[sel] = np.arange(sel.size)
     exp = oracle_table(oracle, sel.size, d, w, 17, remap[items[m]], users[m], None)
-    assert same(got["waves"][0].numpy()[sel].astype(np.float64), exp)
+    with SketchTable(n, depth=d, width=w, seed=17) as t:
+        t.ingest(items, users)
+        t.finalize()
+        check_sampled_owners(oracle, t, sel, exp)
 
 
 @pytest.mark.parametrize("split", ["1024", "4096"])
@@ -954,14 +939,11 @@ def test_lower_split_threshold_same_table(oracle, split, monkeypatch):
     assert same(got[(split, False)][0].numpy()[sel].astype(np.float64), exp)
 
 
-def test_early_slices_same_table(oracle, monkeypatch):
-    """CMS_EARLY_SLICES=1: the hot-routed owners of more than the split
-    threshold are built beside pass 2 of the partition (k_early_plan,
-    k_build_slices on a stream of their own) and the plan skips them: the
-    table, the forms, the norms (through the similarities) and the row
-    maxima equal the default build's, and the heaviest owners equal the
+def test_rebuild_on_reset_handle_matches_oracle(oracle):
+    """Two builds on one reset handle (the second reuses the handle's hot
+    slots and scratch) of owners of many, several and two slices over a Zipf
+    tail: the heaviest owners' counters, forms and similarities match the
     oracle."""
-    import torch
     n, d, w = 4096, 5, 8192
     rng = np.random.Generator(np.random.PCG64(41))
     # owners 0..2: 1.3M / 300K / 70K keys (many, several, two slices), a Zipf tail
@@ -971,23 +953,13 @@ def test_early_slices_same_table(oracle, monkeypatch):
     users = np.concatenate([rng.integers(0, 5_000_000, sum(h.size for h in heavy)), tail_users]).astype(np.int64)
     perm = rng.permutation(items.size)
     items, users = items[perm], users[perm]
-    got = {}
-    for mode in ("0", "1"):
-        monkeypatch.setenv("CMS_EARLY_SLICES", mode)
-        with SketchTable(n, depth=d, width=w, seed=13) as t:
-            for _ in range(2):  # twice: the second build reuses the handle's slots and scratch
-                t.reset()
-                t.ingest(items, users)
-                t.finalize()
-            got[mode] = (t.read_counters_device().cpu(), t.owner_forms()[0],
-                         np.stack([t.similarities(q, np.arange(n)) for q in (0, 1, 2, 3, 100)]),
-                         t.stats()["hot_rows"])
-            torch.cuda.synchronize()
-    assert torch.equal(got["0"][0], got["1"][0])
-    assert np.array_equal(got["0"][1], got["1"][1])
-    assert same(got["0"][2], got["1"][2])
-    assert got["1"][3] >= 3
     sel = np.array([0, 1, 2, 3])
     m = np.isin(items, sel)
     exp = oracle_table(oracle, sel.size, d, w, 13, items[m], users[m], None)
-    assert same(got["1"][0].numpy()[sel].astype(np.float64), exp)
+    with SketchTable(n, depth=d, width=w, seed=13) as t:
+        for _ in range(2):  # twice: the second build reuses the handle's slots and scratch
+            t.reset()
+            t.ingest(items, users)
+            t.finalize()
+        assert t.stats()["hot_rows"] >= 3
+        check_sampled_owners(oracle, t, sel, exp)
