@@ -511,47 +511,77 @@ __global__ __launch_bounds__(kBuildThreads) __attribute__((amdgpu_waves_per_eu(k
 
 // Owner classes of a fresh build with forms: rows holding a u32 slot (split
 // owners and masses >= 2^16: k_build_rows), byte-class rows (k_build_nibbles
-// finds them itself) and the rest, the mid class (k_build_mid).  Each wave
-// appends its rows with one atomic per list.
+// finds them itself) and the rest, the mid class (k_build_mid), in two lists:
+// the CACHED owners (their keys fit k_build_mid's registers) and the STREAMED
+// ones, those above kStreamBigKeys keys first (a persistent grid that starts
+// the long owners first ends with the short ones).
 // Rows of chunks of kClassChunk owners per workgroup: the class lists are
 // gathered in LDS (wave-aggregated LDS counters) and reserved with one global
-// atomic per chunk and list -- with one atomic per wave the two list counters
+// atomic per chunk and list -- with one atomic per wave the list counters
 // took ~200 us of contention at 1M owners.
+//
+// A mid list is TWO-ENDED: cnt[0] owners from the front of its cap entries,
+// cnt[1] more from the back.  The streamed list holds the long owners in
+// front and the others behind; the cached list holds the cached owners behind
+// and takes in front the streamed owners that the one-pass kernel sends back.
+constexpr int kMidThreads = 256;  // threads per owner (a workgroup) of the row-at-a-time mid build
+constexpr int64_t kMidCachedKeys = (int64_t)kMidThreads * kKeyRegs;
+constexpr int64_t kStreamBigKeys = 4096;
+__device__ __forceinline__ int32_t list2_at(const int32_t* list, uint32_t cap, uint32_t nfront, uint32_t i) {
+  return i < nfront ? list[i] : list[cap - 1u - (i - nfront)];
+}
+// counters of the class lists (one zeroed block per build)
+enum { kCntSlot = 0, kCntMid = 1 /* front, back */, kCntStream = 3 /* front, back */, kCntTicket = 5, kCntWords = 8 };
 constexpr int kClassChunk = 4096;
 __global__ __launch_bounds__(256) void k_build_classes(const int64_t* lo_, const int64_t* hi_, int64_t nrows,
                                                        const int32_t* hidx, const uint64_t* bound, int32_t* slot_list,
-                                                       int32_t* mid_list, uint32_t* cnt /* [0] slot, [1] mid */) {
-  __shared__ int32_t s_slot[kClassChunk], s_mid[kClassChunk];
-  __shared__ uint32_t s_n[2], s_b[2];
+                                                       int32_t* mid_list, int32_t* stream_list, uint32_t* cnt) {
+  // both two-ended, as the lists they feed (an owner is in one class): slot
+  // rows from the front of s_own and cached owners from its back, long
+  // streamed owners from the front of s_str and short ones from its back
+  __shared__ int32_t s_own[kClassChunk], s_str[kClassChunk];
+  __shared__ uint32_t s_n[4], s_b[4];  // slot, cached, streamed long, streamed short
   const int lane = (int)__lane_id();
   const int tid = threadIdx.x;
+  const uint32_t cap = (uint32_t)nrows;
   const unsigned long long below = (1ULL << lane) - 1ULL;
   for (int64_t r0 = (int64_t)blockIdx.x * kClassChunk; r0 < nrows; r0 += (int64_t)gridDim.x * kClassChunk) {
-    if (tid < 2) s_n[tid] = 0;
+    if (tid < 4) s_n[tid] = 0;
     __syncthreads();
     for (int64_t r = r0 + tid; r < r0 + kClassChunk; r += 256) {  // (whole waves: the ballots)
-      bool is_slot = false, is_mid = false;
+      bool is[4] = {false, false, false, false};
       if (r < nrows) {
         const int32_t sl = hidx[r];
-        is_slot = sl >= 0;
-        is_mid = !is_slot && !byte_class(sl, hi_[r] - lo_[r], bound[r]);
+        const int64_t m = hi_[r] - lo_[r];
+        is[0] = sl >= 0;
+        const bool is_mid = !is[0] && !byte_class(sl, m, bound[r]);
+        is[1] = is_mid && m <= kMidCachedKeys;
+        is[2] = is_mid && m > kStreamBigKeys;
+        is[3] = is_mid && !is[1] && !is[2];
       }
-      const unsigned long long ms = __ballot(is_slot), mm = __ballot(is_mid);
-      uint32_t b0 = 0, b1 = 0;
-      if (lane == 0) {
-        if (ms) b0 = atomicAdd(&s_n[0], (uint32_t)__popcll(ms));
-        if (mm) b1 = atomicAdd(&s_n[1], (uint32_t)__popcll(mm));
+      unsigned long long mk[4];
+      uint32_t b[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        mk[k] = __ballot(is[k]);
+        if (lane == 0 && mk[k]) b[k] = atomicAdd(&s_n[k], (uint32_t)__popcll(mk[k]));
+        b[k] = (uint32_t)__shfl((int)b[k], 0, 64) + (uint32_t)__popcll(mk[k] & below);
       }
-      b0 = (uint32_t)__shfl((int)b0, 0, 64);
-      b1 = (uint32_t)__shfl((int)b1, 0, 64);
-      if (is_slot) s_slot[b0 + __popcll(ms & below)] = (int32_t)r;
-      if (is_mid) s_mid[b1 + __popcll(mm & below)] = (int32_t)r;
+      if (is[0]) s_own[b[0]] = (int32_t)r;
+      if (is[1]) s_own[kClassChunk - 1 - b[1]] = (int32_t)r;
+      if (is[2]) s_str[b[2]] = (int32_t)r;
+      if (is[3]) s_str[kClassChunk - 1 - b[3]] = (int32_t)r;
     }
     __syncthreads();
-    if (tid < 2) s_b[tid] = s_n[tid] ? atomicAdd(&cnt[tid], s_n[tid]) : 0u;
+    if (tid < 4) {
+      const int ci = tid == 0 ? kCntSlot : tid == 1 ? kCntMid + 1 : kCntStream + tid - 2;
+      s_b[tid] = s_n[tid] ? atomicAdd(&cnt[ci], s_n[tid]) : 0u;
+    }
     __syncthreads();
-    for (uint32_t i = tid; i < s_n[0]; i += 256) slot_list[s_b[0] + i] = s_slot[i];
-    for (uint32_t i = tid; i < s_n[1]; i += 256) mid_list[s_b[1] + i] = s_mid[i];
+    for (uint32_t i = tid; i < s_n[0]; i += 256) slot_list[s_b[0] + i] = s_own[i];
+    for (uint32_t i = tid; i < s_n[1]; i += 256) mid_list[cap - 1u - (s_b[1] + i)] = s_own[kClassChunk - 1 - i];
+    for (uint32_t i = tid; i < s_n[2]; i += 256) stream_list[s_b[2] + i] = s_str[i];
+    for (uint32_t i = tid; i < s_n[3]; i += 256) stream_list[cap - 1u - (s_b[3] + i)] = s_str[kClassChunk - 1 - i];
     __syncthreads();
   }
 }
@@ -570,16 +600,15 @@ __global__ __launch_bounds__(256) void k_build_classes(const int64_t* lo_, const
 constexpr int kMidListKeys = kBuildThreads * kKeyRegs;
 // keys per thread in flight per step of an uncached owner's row pass
 constexpr int kMidRowKeys = 4;
-constexpr int kMidThreads = 256;  // threads per owner (a workgroup)
-// MT is only ever kMidThreads: the parameter stays so that the kernels' names
-// do (profiles and the benchmark's kernel patterns are keyed on them)
+// mid_rows is the body of k_build_mid<SV, D, kMidThreads> (the kernel follows
+// mid_streamed below): the cached owners, and the streamed ones that are
+// weighted, do not start at u8 or passed 255 in mid_streamed's image.
 template <int SV, int D, int MT>
-// 4 waves per SIMD: the key prefetch needs more than the 80 VGPRs of 6
-// (it spilled there); the build measured the same (profiles/r04/ab_*_s5)
-__global__ __launch_bounds__(MT) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_build_mid(
-    const int64_t* lo_, const int64_t* hi_, Keys keys, const float* vals, HashParams hp,
-    const int32_t* list, const uint32_t* list_cnt, TableView tv, int32_t* hidx_w, uint32_t* cbound,
-    uint64_t* row_mass, uint64_t* norm, uint32_t* rowmax, uint32_t* flags, int list_keys, int u4_keys, int u8_keys) {
+__device__ __forceinline__ void mid_rows(
+    const int64_t* lo_, const int64_t* hi_, const Keys& keys, const float* vals, const HashParams& hp,
+    const int32_t* list, const uint32_t* list_cnt, uint32_t cap, const TableView& tv, int32_t* hidx_w,
+    uint32_t* cbound, uint64_t* row_mass, uint64_t* norm, uint32_t* rowmax, uint32_t* flags, int list_keys,
+    int u4_keys, int u8_keys) {
   static_assert(MT == kMidThreads, "one instantiation per depth");
   constexpr int MTH = MT;        // threads per owner (a workgroup)
   constexpr int MKR = kKeyRegs;  // key registers per thread: 1024 keys cached per owner
@@ -589,9 +618,9 @@ __global__ __launch_bounds__(MT) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   __shared__ uint32_t s_max, s_ovf;
   const int tid = threadIdx.x;
   const int w = (int)hp.width;
-  const uint32_t count = *list_cnt;
+  const uint32_t nfront = list_cnt[0], count = nfront + list_cnt[1];
   for (uint32_t li = blockIdx.x; li < count; li += gridDim.x) {
-    const int64_t row = list[li];
+    const int64_t row = list2_at(list, cap, nfront, li);
     const int64_t lo = lo_[row], hi = hi_[row];
     const bool cached = (hi - lo) <= (int64_t)MTH * MKR;
     uint64_t kp[MKR];
@@ -853,6 +882,173 @@ __global__ __launch_bounds__(MT) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     }
     __syncthreads();  // shared sums consumed before the next owner
   }
+}
+
+// STREAMED mid owners (more than kMidCachedKeys keys) of a unit-increment
+// build: ONE key pass for all d sketch rows, the shape of k_build_slices on a
+// [d][w] u8 image (d*w bytes, 40 KB at config 3).  mid_rows walks such an
+// owner's keys d times, one sketch row each, every step's loads waited for
+// before its keys are hashed; here the tokens are fetched a step ahead,
+// resolved once per key and hashed by each_bucket<D>.  512 threads per image:
+// four images fill a CU's LDS, and with 256 threads they were 16 waves per CU
+// (the k_build_image experiment, which also swept its image for the few
+// hundred keys of a cached owner); four 512-thread workgroups are the CU's
+// whole wave budget, and only owners above 1024 keys pay the sweep.
+// The image takes all the dynamic LDS and the kernel has no static LDS (a
+// word of static LDS would cost the fourth image of a CU): the workgroup's
+// reductions and its next ticket go through the image's own words after the
+// sweep has read them.
+// A counter that passes 255 carries into the neighbouring byte (or out of
+// its word), which takes 255 (or 256) off the image's byte sum: the sweep sums
+// the bytes, and an owner whose sum is not d times its key count is sent back
+// (the front of the cached list, redo) for mid_rows' u16 rows.  The adds
+// therefore need not return the old counter -- with returning adds and a flag
+// per add the kernel spilled at 80 VGPRs.  An owner that does not start at u8
+// (Tunables::mid_u4_keys / mid_u8_keys) is sent back too: the stored form of
+// every owner is the one mid_rows alone gives it.  Workgroups take owners
+// from a ticket counter: the owners' key counts span 16x.
+constexpr int kStreamThreads = 512;
+constexpr int kStreamPer = 2;  // keys per thread per step (the next step's loads in flight; 4 spilled at 64 VGPRs)
+// LDS words the reductions need: the next ticket, then per wave d sums of squares, a maximum and a byte sum
+constexpr int kStreamRedWords = 1 + (kStreamThreads / 64) * (CMS_MAX_DEPTH + 2);
+template <int SV, int D>
+__device__ __forceinline__ void mid_streamed(const int64_t* lo_, const int64_t* hi_, const Keys& keys,
+                                             const HashParams& hp, const int32_t* list, const uint32_t* list_cnt,
+                                             uint32_t cap, const TableView& tv, int32_t* hidx_w, uint32_t* cbound,
+                                             uint64_t* row_mass, uint64_t* norm, uint32_t* rowmax, int32_t* redo,
+                                             uint32_t* redo_cnt, uint32_t* ticket, int u4_keys, int u8_keys) {
+  extern __shared__ __align__(16) uint32_t lds[];  // the [d][w] u8 image (at least kStreamRedWords words)
+  constexpr int T = kStreamThreads;
+  constexpr int NW = T / 64;
+  constexpr int RS = CMS_MAX_DEPTH + 2;  // reduction words per wave
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int w = (int)hp.width;
+  const int depth = D > 0 ? D : hp.depth;
+  const int nq = w >> 4;  // uint4 per u8 sketch row (w % 32 == 0)
+  const uint32_t nfront = list_cnt[0], count = nfront + list_cnt[1];
+  uint4* l4 = reinterpret_cast<uint4*>(lds);
+  uint32_t* red = lds + 1;
+  if (tid == 0) lds[0] = atomicAdd(ticket, 1u);
+  __syncthreads();
+  uint32_t li = lds[0];
+  while (li < count) {  // (uniform)
+    __syncthreads();  // the ticket and the last owner's sums are read before the image is zeroed
+    const int64_t row = list2_at(list, cap, nfront, li);
+    const int64_t lo = lo_[row], hi = hi_[row];
+    const int64_t m = hi - lo;
+    const bool u8_start = m > u4_keys && m <= u8_keys;  // else mid_rows' owner
+    uint32_t mine = 0;  // lane r holds its wave's sum of squares of sketch row r
+    uint32_t bytes = 0;  // sum of the image's bytes: d * m unless a counter passed 255
+    u16x2 pm = {0, 0};
+    if (u8_start) {
+      for (int j = tid; j < depth * nq; j += T) l4[j] = make_uint4(0, 0, 0, 0);
+      __syncthreads();
+      constexpr int64_t kStep = (int64_t)kStreamPer * T;
+      uint64_t nx[kStreamPer];
+      auto fetch = [&](int64_t base) {
+#pragma unroll
+        for (int u = 0; u < kStreamPer; ++u) {
+          const int64_t i = base + tid + (int64_t)u * T;
+          nx[u] = i < hi ? keys.raw(i) : 0ULL;
+        }
+      };
+      fetch(lo);
+      for (int64_t base = lo; base < hi; base += kStep) {
+        uint64_t kk[kStreamPer];
+#pragma unroll
+        for (int u = 0; u < kStreamPer; ++u) kk[u] = nx[u];
+        if (base + kStep < hi) fetch(base + kStep);
+#pragma unroll
+        for (int u = 0; u < kStreamPer; ++u) {
+          if (base + tid + (int64_t)u * T >= hi) continue;  // (a raw key may be any 64-bit value)
+          each_bucket<D>(hp, keys.resolve(kk[u]), [&](int r, uint32_t bk) {
+            const uint32_t c = (uint32_t)r * (uint32_t)w + bk;
+            atomicAdd(&lds[c >> 2], 1u << ((c & 3u) << 3));
+          });
+        }
+      }
+      __syncthreads();
+      // the image leaves as it is (an owner that overflowed is rewritten whole
+      // by mid_rows); each sketch row's sum of squares by v_dot4 of its bytes,
+      // the largest counter by packed u16 maxima of the even and the odd bytes
+      uint4* d4 = reinterpret_cast<uint4*>(tv.row16(row));  // the row's slot (64-B aligned)
+      auto sweep_row = [&](int r) {
+        uint32_t sq = 0;  // <= 255 * the key count < 2^32
+        for (int j = tid; j < nq; j += T) {
+          const uint4 v = l4[r * nq + j];
+          const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            sq = __builtin_amdgcn_udot4(x[q], x[q], sq, false);
+            bytes = __builtin_amdgcn_udot4(x[q], 0x01010101u, bytes, false);
+            pm = __builtin_elementwise_max(pm, __builtin_elementwise_max(__builtin_bit_cast(u16x2, x[q] & 0x00FF00FFu),
+                                                                         __builtin_bit_cast(u16x2, (x[q] >> 8) & 0x00FF00FFu)));
+          }
+          store_row(d4 + r * nq + j, v, SV);
+        }
+        sq = wave_sum_u32(sq);
+        if (lane == r) mine = sq;
+      };
+#pragma unroll 1
+      for (int r = 0; r < depth; ++r) sweep_row(r);
+    }
+    uint32_t vmax = max((uint32_t)pm.x, (uint32_t)pm.y);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) vmax = max(vmax, (uint32_t)__shfl_xor((int)vmax, o, 64));
+    bytes = wave_sum_u32(bytes);  // <= d * m < 2^32
+    __syncthreads();  // the image is read out: its first words take the reductions
+    if (lane < depth) red[wv * RS + lane] = mine;
+    if (lane == 0) {
+      red[wv * RS + CMS_MAX_DEPTH] = vmax;
+      red[wv * RS + CMS_MAX_DEPTH + 1] = bytes;
+    }
+    if (tid == 0) lds[0] = atomicAdd(ticket, 1u);
+    __syncthreads();
+    uint32_t mx = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+      mx = max(mx, red[k * RS + CMS_MAX_DEPTH]);
+      total += red[k * RS + CMS_MAX_DEPTH + 1];
+    }
+    if (!u8_start || total != (uint32_t)depth * (uint32_t)m) {
+      if (tid == 0) redo[atomicAdd(redo_cnt, 1u)] = (int32_t)row;
+    } else {
+      if (tid < depth) {
+        uint64_t s = 0;
+#pragma unroll
+        for (int k = 0; k < NW; ++k) s += red[k * RS + tid];
+        norm[row * depth + tid] = s;
+      }
+      if (tid == 0) {
+        rowmax[row] = mx;
+        row_mass[row] = (uint64_t)m;  // unit increments
+        hidx_w[row] = kFormU8;
+        cbound[row] = mx;
+      }
+    }
+    li = lds[0];
+  }
+}
+
+// The mid-class kernel: MT == kMidThreads walks a list with mid_rows (a
+// persistent grid with a fixed stride), MT == kStreamThreads takes a streamed
+// list's owners by ticket with mid_streamed.  One name for both: profiles and
+// the benchmark's kernel patterns are keyed on it.
+template <int SV, int D, int MT>
+// mid_rows, 4 waves per SIMD: the key prefetch needs more than the 80 VGPRs
+// of 6 (it spilled there); the build measured the same (profiles/r04/ab_*_s5).
+// mid_streamed, 8: four 512-thread workgroups per CU.
+__global__ __launch_bounds__(MT) __attribute__((amdgpu_waves_per_eu(MT == kStreamThreads ? 8 : 4, 8))) void k_build_mid(
+    const int64_t* lo_, const int64_t* hi_, Keys keys, const float* vals, HashParams hp,
+    const int32_t* list, const uint32_t* list_cnt /* front, back */, uint32_t cap, TableView tv, int32_t* hidx_w,
+    uint32_t* cbound, uint64_t* row_mass, uint64_t* norm, uint32_t* rowmax, uint32_t* flags, int list_keys,
+    int u4_keys, int u8_keys, int32_t* redo, uint32_t* redo_cnt, uint32_t* ticket) {
+  if constexpr (MT == kStreamThreads)
+    mid_streamed<SV, D>(lo_, hi_, keys, hp, list, list_cnt, cap, tv, hidx_w, cbound, row_mass, norm, rowmax, redo,
+                        redo_cnt, ticket, u4_keys, u8_keys);
+  else
+    mid_rows<SV, D, MT>(lo_, hi_, keys, vals, hp, list, list_cnt, cap, tv, hidx_w, cbound, row_mass, norm, rowmax,
+                        flags, list_keys, u4_keys, u8_keys);
 }
 
 // Byte-class owners (byte_class): ONE WAVE per owner, four owners per
@@ -1475,19 +1671,20 @@ int ingest_spans_device(cms_handle* h, const int64_t* d_lo, const int64_t* d_hi,
       // the ones a counter >= 16 sends back) and mid rows -> k_build_mid on the
       // side stream, so the classes' kernels overlap (their tails no longer
       // leave CUs idle)
-      CMS_HIP(h->ws_blist.ensure(sizeof(int32_t) * (size_t)(2 * n + 2)));
+      CMS_HIP(h->ws_blist.ensure(sizeof(int32_t) * (size_t)(3 * n + kCntWords)));
       int32_t* slot_list = h->ws_blist.as<int32_t>();
-      int32_t* mid_list = slot_list + n;
-      uint32_t* lcnt = reinterpret_cast<uint32_t*>(mid_list + n);  // [0] slot rows, [1] mid rows
+      int32_t* mid_list = slot_list + n;     // two-ended: sent-back streamed owners, cached owners
+      int32_t* stream_list = mid_list + n;   // two-ended: owners above kStreamBigKeys keys, the others
+      uint32_t* lcnt = reinterpret_cast<uint32_t*>(stream_list + n);  // kCnt*
       CMS_HIP(h->ws_plist.ensure(sizeof(int32_t) * (size_t)(n + 1)));
       int32_t* redo = h->ws_plist.as<int32_t>();
       uint32_t* redo_cnt = reinterpret_cast<uint32_t*>(redo + n);
-      CMS_HIP(hipMemsetAsync(lcnt, 0, 2 * sizeof(uint32_t), h->stream));
+      CMS_HIP(hipMemsetAsync(lcnt, 0, kCntWords * sizeof(uint32_t), h->stream));
       CMS_HIP(hipMemsetAsync(redo_cnt, 0, sizeof(uint32_t), h->stream));
       hipLaunchKernelGGL(k_build_classes,
                          dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kClassChunk - 1) / kClassChunk, 1024))),
                          dim3(256), 0, h->stream, d_lo, d_hi, n, h->d_hidx, h->ws_bound.as<uint64_t>(), slot_list,
-                         mid_list, lcnt);
+                         mid_list, stream_list, lcnt);
       CMS_HIP(hipGetLastError());
       if (h->plan_side_active) return set_error(CMS_E_STATE, "internal: side stream used while swapped for the plan");
       hipStream_t side = h->side_stream ? h->side_stream : h->stream;
@@ -1527,11 +1724,36 @@ int ingest_spans_device(cms_handle* h, const int64_t* d_lo, const int64_t* d_hi,
       auto kmid = h->p.depth == 5   ? k_build_mid<kBuildStoreForm, 5, kMidThreads>
                   : h->p.depth == 4 ? k_build_mid<kBuildStoreForm, 4, kMidThreads>
                                     : k_build_mid<kBuildStoreForm, 0, kMidThreads>;
-      hipLaunchKernelGGL(kmid, dim3((unsigned)std::min<int64_t>(n, (int64_t)h->num_cus * kMidGridPerCu)),
-                         dim3(kMidThreads), mid_lds, side2, d_lo, d_hi, keys, d_val, h->hp, (const int32_t*)mid_list,
-                         (const uint32_t*)(lcnt + 1), h->tview(), h->d_hidx, h->d_cbound, h->d_row_mass, h->d_norm,
-                         h->d_rowmax, h->d_flags, lists_allowed(h) ? kMidListKeys : 0, h->tune.mid_u4_keys,
-                         h->tune.mid_u8_keys);
+      auto launch_mid = [&](auto kern, int threads, unsigned grid, size_t klds, const int32_t* list, uint32_t* cnt) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), klds, side2, d_lo, d_hi, keys, d_val, h->hp, list,
+                           (const uint32_t*)cnt, (uint32_t)n, h->tview(), h->d_hidx, h->d_cbound, h->d_row_mass,
+                           h->d_norm, h->d_rowmax, h->d_flags, lists_allowed(h) ? kMidListKeys : 0,
+                           h->tune.mid_u4_keys, h->tune.mid_u8_keys, mid_list, lcnt + kCntMid, lcnt + kCntTicket);
+      };
+      const unsigned mid_grid = (unsigned)std::min<int64_t>(n, (int64_t)h->num_cus * kMidGridPerCu);
+      // the streamed owners first (the long work), in one key pass each when
+      // the increments are units (forms: the [d][w] u8 image fits kFormLdsMax);
+      // then the cached owners behind the streamed ones sent back for u16 rows
+      bool one_pass = !d_val && h->hp.frac_bits == 0;
+#ifdef CMS_BUILD_NO_STREAMED  // bound analysis only: the streamed owners row at a time (k_build_mid once per list)
+      one_pass = false;
+#endif
+      if (one_pass) {
+        auto kstr = h->p.depth == 5   ? k_build_mid<kBuildStoreForm, 5, kStreamThreads>
+                    : h->p.depth == 4 ? k_build_mid<kBuildStoreForm, 4, kStreamThreads>
+                                      : k_build_mid<kBuildStoreForm, 0, kStreamThreads>;
+        const size_t str_lds = std::max<size_t>((size_t)h->dw, sizeof(uint32_t) * kStreamRedWords);
+        if (h->stream_wgs_per_cu <= 0) {  // a grid that is resident whole (workgroups take owners by ticket)
+          int per_cu = 0;
+          CMS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kstr, kStreamThreads, str_lds));
+          h->stream_wgs_per_cu = std::max(1, per_cu);
+        }
+        launch_mid(kstr, kStreamThreads, (unsigned)std::min<int64_t>(n, (int64_t)h->num_cus * h->stream_wgs_per_cu),
+                   str_lds, stream_list, lcnt + kCntStream);
+      } else {
+        launch_mid(kmid, kMidThreads, mid_grid, mid_lds, stream_list, lcnt + kCntStream);
+      }
+      launch_mid(kmid, kMidThreads, mid_grid, mid_lds, mid_list, lcnt + kCntMid);
       hipLaunchKernelGGL(k_build_bytes<kBuildStoreForm>, dim3((unsigned)std::min<int64_t>(n, (int64_t)h->num_cus * 2)),
                          dim3(kBuildThreads), (size_t)h->dw, side, d_lo, d_hi, keys, d_val, h->hp, redo, redo_cnt,
                          h->tview(), h->d_hidx, h->d_cbound, h->d_row_mass, h->d_norm, h->d_rowmax, h->d_flags);

@@ -263,6 +263,7 @@ struct cms_handle {
   cms::Tunables tune;
   int device = 0;
   int num_cus = 256;  // compute units of the device (persistent grids)
+  int stream_wgs_per_cu = 0;  // resident workgroups per CU of the streamed mid build (occupancy query, once)
   hipStream_t stream = nullptr;
   // side stream of the row build: the byte-class kernels run beside the slot
   // rows (ordered by ev_fork2 / ev_join2 on the handle's stream), and the
@@ -312,7 +313,7 @@ struct cms_handle {
   bool forms_ok = false;            // dw % 32 == 0: fresh builds may store u8 / nibble forms
   cms::DevBuf hot_tab;              // [hot_cap][d][w] u32 counters of the hot rows
   cms::DevBuf ws_bound, ws_force, ws_plist;  // promotion scratch: u64 [n], u8 [n], i32 [n] + count
-  cms::DevBuf ws_blist;                      // row build: slot-row and mid-class row lists + counts
+  cms::DevBuf ws_blist;                      // row build: slot-row, cached-mid and streamed-mid row lists + counts
   cms::DevBuf ws_layout;                     // row layout: capacities / scan (u32 [2n + ...]); widen: movers
   int64_t hot_cap = 0, hot_used = 0;
   cms::TableView tview() const {
