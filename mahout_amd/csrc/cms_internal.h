@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/mahout_cms.h"
+#include "cms_forms.h"
 #include "cms_hash.h"
 
 namespace cms {
@@ -102,35 +103,7 @@ struct PendingEvent {
 // list row takes no in-place adds (capacity 0: any write widens it to u16
 // first); whole-row readers expand it per sketch row (list_* helpers).
 constexpr uint64_t kNarrowLimit = 1ULL << 16;
-constexpr int32_t kFormU16 = -1, kFormU8 = -2, kFormU4 = -3, kFormU2 = -4, kFormU1 = -5, kFormList = -6;
-constexpr uint32_t form_cap(int32_t form) {
-  return form == kFormList ? 0u : form == kFormU1 ? 1u : form == kFormU2 ? 3u : form == kFormU4 ? 15u
-       : form == kFormU8 ? 255u : 65535u;
-}
-
-constexpr int64_t kRowAlign = 64;  // u16 units (128 B: an L2 line, so no two rows share one) per arena allocation unit
-__host__ __device__ constexpr int64_t slot_units(int64_t dw) { return (dw + kRowAlign - 1) / kRowAlign * kRowAlign; }
-// off[row] bits 0-2 (the offset is a multiple of kRowAlign): the widest form
-// the row's place holds -- a row is written in place only in a form no wider.
-// kCapNone: a list row's place, or the shared zero row (offset 0).
-constexpr int64_t kCapMask = 7;
-enum : int { kCapNone = 0, kCapU1 = 1, kCapU2 = 2, kCapU4 = 3, kCapU8 = 4, kCapU16 = 5 };
-__host__ __device__ constexpr int form_class(int32_t f) {
-  return f == kFormU1 ? kCapU1 : f == kFormU2 ? kCapU2 : f == kFormU4 ? kCapU4 : f == kFormU8 ? kCapU8
-       : f == kFormU16 ? kCapU16 : kCapNone;
-}
-// u16 units a form's row takes in the arena (rounded to kRowAlign)
-__host__ __device__ constexpr int64_t class_units(int c, int64_t dw) {
-  return c == kCapU16 ? slot_units(dw)
-       : ((c == kCapU8 ? dw / 2 : c == kCapU4 ? dw / 4 : c == kCapU2 ? dw / 8 : c == kCapU1 ? dw / 16 : 0) +
-          kRowAlign - 1) / kRowAlign * kRowAlign;
-}
-// the widest form a place of `units` u16 holds
-__host__ __device__ constexpr int class_of_units(int64_t units, int64_t dw) {
-  return units >= class_units(kCapU16, dw) ? kCapU16 : units >= class_units(kCapU8, dw) ? kCapU8
-       : units >= class_units(kCapU4, dw) ? kCapU4 : units >= class_units(kCapU2, dw) ? kCapU2
-       : units >= class_units(kCapU1, dw) && dw >= 16 ? kCapU1 : kCapNone;
-}
+// (the forms, the place classes and widen_rows' per-row decisions: cms_forms.h)
 
 struct TableView {
   uint16_t* t16;        // the narrow-row arena (row r at off[r] & ~kCapMask)

@@ -126,34 +126,10 @@ int promote_rows(cms_handle* h, const uint64_t* d_bound, const uint8_t* d_force,
 // has keys -- the build rewrites every such row through its u16 / u32 image
 // even when all its increments are 0 (no mass added).  A listed row's cbound
 // becomes its bound after the write, which picks the form it widens to.
-__device__ __forceinline__ int form_bits(int32_t f) {  // counter bits of a form (0: a list row)
-  return f == kFormList ? 0 : f == kFormU1 ? 1 : f == kFormU2 ? 2 : f == kFormU4 ? 4 : f == kFormU8 ? 8 : 16;
-}
-
-// The form a listed row is rewritten in: the narrowest form wider than its
-// own whose capacity holds its new bound nb (u16 for an accumulate build) --
-// a 2-bit row that one more pair lifts to 4 becomes a 4-bit row.  The zero
-// row counts as a list row (it holds nothing of its own).
-// the smallest place a moved row takes (kCap class): a mover whose target
-// form fits a u8 row takes a u8 place, one past it a whole slot.  With the
-// rows' bounds from their tracked maxima most rows never pass u8: after the
-// 1B-pair config-5 stream 78.7 GB in use against 102 GB with whole slots
-// for every mover (scripts/stream_compact_probe.py)
-#ifndef CMS_MOVE_CLASS
-#define CMS_MOVE_CLASS 4
-#endif
 // widening bounds from the tracked row maxima (0: the accumulated cbound alone)
 #ifndef CMS_WIDEN_ROWMAX
 #define CMS_WIDEN_ROWMAX 1
 #endif
-__device__ __forceinline__ int32_t widen_target(int32_t f, uint32_t nb, int to_u16, int w) {
-  if (to_u16) return kFormU16;
-  if (f == kFormList && nb <= 1u && (w & 127) == 0) return kFormU1;
-  if (form_bits(f) < 2 && nb <= 3u && (w & 63) == 0) return kFormU2;
-  if (form_bits(f) < 4 && nb <= 15u) return kFormU4;
-  if (form_bits(f) < 8 && nb <= 255u) return kFormU8;
-  return kFormU16;
-}
 
 // A listed row is rewritten in place when its place holds the target form
 // (its kCap class), else it moves to a place of class CMS_MOVE_CLASS (or a
@@ -181,47 +157,39 @@ __global__ void k_widen_mark(const uint64_t* bound, const uint64_t* old_mass, co
       // are tracked) bounds it more tightly than the accumulated cbound
       const uint64_t cur = rowmax ? min<uint64_t>(cbound[r], rowmax[r]) : (uint64_t)cbound[r];
       const uint64_t nb = cur + (b - m);
-      need = all_touched || nb > (uint64_t)form_cap(f) || o == 0;
+      need = widen_needed(f, o == 0, nb, all_touched != 0);
       nbv = (uint32_t)min<uint64_t>(nb, 0xFFFFFFFFull);
       cbound[r] = nbv;  // <= the capacity of the form it keeps or takes
     }
     if (need) {
-      const int32_t tf = widen_target(o == 0 ? kFormList : f, nbv, to_u16, w);
-      const int tc = form_class(tf);
+      const int32_t tf = widen_target(f, o == 0, nbv, to_u16, w);
       const uint32_t i = atomicAdd(cnt, 1u);
       list[i] = (int32_t)r;
       tfa[i] = (int8_t)tf;
-      const int mc = tc >= CMS_MOVE_CLASS ? kCapU16 : CMS_MOVE_CLASS;  // the class of a mover's new place
-      mv[i] = (o != 0 && cc >= tc) ? -1 : (int32_t)atomicAdd(cnt + 1, (uint32_t)(class_units(mc, dw) / kRowAlign));
+      mv[i] = widen_in_place(o == 0, cc, tf)
+                  ? -1
+                  : (int32_t)atomicAdd(cnt + 1, (uint32_t)(class_units(widen_move_class(tf), dw) / kRowAlign));
     }
   }
 }
 
-// 16 counters v[0..16) packed at 32 / C bits into C-counter words at w32[j / C ...]
-template <int C>
-__device__ __forceinline__ void pack16(const uint32_t (&v)[16], uint32_t* w32, int64_t j) {
-#pragma unroll
-  for (int q = 0; q < 16; q += C) {
-    uint32_t word = 0;
-#pragma unroll
-    for (int k = 0; k < C; ++k) word |= v[q + k] << (k * (32 / C));
-    w32[(j + q) / C] = word;
-  }
-}
-
 // One workgroup per listed row, rewritten (in place, or into a mover's new
-// slot at base + mv[i] * kRowAlign) in its target form tfa[i] (widen_target:
-// the narrowest form
-// wider than its own whose capacity holds its new bound (cbound), u16 for an
-// accumulate build (to_u16) -- a 2-bit row that one more pair lifts to 4
-// becomes a 4-bit row (half the bytes of u8, a quarter of u16).
+// slot at base + mv[i] * kRowAlign) in its target form tfa[i] (cms_forms.h
+// widen_target: the narrowest form wider than its own whose capacity holds
+// its new bound (cbound), u16 for an accumulate build (to_u16) -- a 2-bit row
+// that one more pair lifts to 4 becomes a 4-bit row (half the bytes of u8, a
+// quarter of u16).
 //  * dense forms: the image of counters [c0, c1) at tb >= sb bits covers
 //    bytes [c0 tb/8, c1 tb/8), which hold only old bytes of counters >= c0;
 //    so chunks of 4096 counters go from the top down, each read completely
 //    (16 counters per lane) before any lane writes it.
 //  * list rows: every entry is read first (at most 32 per lane: d <= 32,
 //    m <= 256), then each sketch row is counted in LDS (u8 counters, four per
-//    word: a list row's counters are < 2^8) and leaves packed.
+//    word: a list row's counters are < 2^8) and leaves packed.  An owner on
+//    the zero row goes this way as a list of no entries.
+// Either way the row's stores cover d w tb / 8 bytes from its place's start,
+// and k_widen_mark gave it a place of a class that holds tf (cms_forms.h:
+// widen_in_place / widen_move_class).
 __global__ __launch_bounds__(256) void k_widen_rows(const int32_t* list, const int32_t* mv, const int8_t* tfa,
                                                     const uint32_t* dcount, TableView tv, int64_t* off_w, int64_t base,
                                                     int32_t* hidx) {
@@ -235,12 +203,13 @@ __global__ __launch_bounds__(256) void k_widen_rows(const int32_t* list, const i
     const int32_t f = hidx[r];
     const int32_t tf = tfa[i];
     const int tb = form_bits(tf);
+    const bool zero = tv.off[r] == 0;  // no counters of its own yet
     const uint16_t* src = tv.row16(r);
     const int64_t dst_off = mv[i] >= 0 ? base + (int64_t)mv[i] * kRowAlign : tv.base(r);
     const uint8_t* p8 = reinterpret_cast<const uint8_t*>(src);
     uint32_t* w32 = reinterpret_cast<uint32_t*>(tv.t16 + dst_off);
-    if (f == kFormList) {
-      const uint32_t m = tv.list_m(r);
+    if (widen_recount(f, zero)) {
+      const uint32_t m = zero ? 0u : tv.list_m(r);  // (the zero row: no entries, nothing read)
       const uint32_t ne = (uint32_t)(dw / w) * m;
       uint32_t ent[32];
 #pragma unroll
@@ -249,7 +218,7 @@ __global__ __launch_bounds__(256) void k_widen_rows(const int32_t* list, const i
         ent[q] = 0xFFFFFFFFu;
         if (t < ne) ent[q] = (t / m) << 16 | src[1 + t];  // sketch row, bucket
       }
-      const int cpw = 32 / tb;  // counters per output word
+      const int nw = w / (32 / tb);  // output words per sketch row
       for (int rr = 0; (int64_t)rr * w < dw; ++rr) {
         for (int j = threadIdx.x; j < (w >> 2); j += 256) lc[j] = 0u;
         __syncthreads();  // (the first pass: every entry is also read before any store below)
@@ -259,57 +228,22 @@ __global__ __launch_bounds__(256) void k_widen_rows(const int32_t* list, const i
             atomicAdd(&lc[(ent[q] & 0xFFFFu) >> 2], 1u << ((ent[q] & 3u) * 8u));
         __syncthreads();
         const uint8_t* c8 = reinterpret_cast<const uint8_t*>(lc);
-        for (int q = threadIdx.x; q < w / cpw; q += 256) {
-          uint32_t word = 0;
-          for (int k = 0; k < cpw; ++k) word |= (uint32_t)c8[q * cpw + k] << (k * tb);
-          w32[((int64_t)rr * w) / cpw + q] = word;
-        }
+        for (int q = threadIdx.x; q < nw; q += 256) pack_counts_word(tb, c8, w32, rr, w, q);
         __syncthreads();  // the counts are packed before the next sketch row zeroes them
       }
     } else {
       for (int64_t c0 = ((dw - 1) / kChunk) * kChunk; c0 >= 0; c0 -= kChunk) {
         const int64_t j = c0 + (int64_t)threadIdx.x * 16;  // this lane's 16 counters
         uint32_t v[16];
-        if (j < dw) {
-          if (f == kFormU16) {  // a mover's u16 row (the zero row): copied
-            const uint4 x0 = *reinterpret_cast<const uint4*>(src + j);
-            const uint4 x1 = *reinterpret_cast<const uint4*>(src + j + 8);
-            const uint32_t wv[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = (wv[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
-          } else if (f == kFormU8) {
-            const uint4 x = *reinterpret_cast<const uint4*>(p8 + j);
-            const uint32_t wv[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = (wv[q >> 2] >> ((q & 3) * 8)) & 255u;
-          } else if (f == kFormU2) {
-            const uint32_t x = *reinterpret_cast<const uint32_t*>(p8 + (j >> 2));
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = (x >> (q * 2)) & 3u;
-          } else if (f == kFormU1) {
-            const uint32_t x = *reinterpret_cast<const uint16_t*>(p8 + (j >> 3));
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = (x >> q) & 1u;
-          } else {
-            const uint2 x = *reinterpret_cast<const uint2*>(p8 + (j >> 1));
-            const uint32_t wv[2] = {x.x, x.y};
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = (wv[q >> 3] >> ((q & 7) * 4)) & 15u;
-          }
-        }
+        if (j < dw) unpack16(f, p8, j, v);
         __syncthreads();  // the whole chunk is read before any lane overwrites it
-        if (j < dw) {  // 16 counters at tb bits: tb / 2 words from word j tb / 32
-          if (tb == 2) pack16<16>(v, w32, j);
-          else if (tb == 4) pack16<8>(v, w32, j);
-          else if (tb == 8) pack16<4>(v, w32, j);
-          else pack16<2>(v, w32, j);
-        }
+        if (j < dw) pack16_bits(tb, v, w32, j);  // tb / 2 words from word j tb / 32
         __syncthreads();  // the next (lower) chunk's old bytes are read after these stores
       }
     }
     if (threadIdx.x == 0) {
       hidx[r] = tf;
-      if (mv[i] >= 0) off_w[r] = dst_off | (form_class(tf) >= CMS_MOVE_CLASS ? kCapU16 : CMS_MOVE_CLASS);  // (k_widen_mark)
+      if (mv[i] >= 0) off_w[r] = dst_off | widen_move_class(tf);  // (k_widen_mark)
     }
   }
 }

@@ -170,6 +170,11 @@ def test_compact_arena_regrows_and_shrinks(oracle, monkeypatch, vmm):
         t.finalize()
         tb_more = check(t, np.concatenate([small_i, more_i]), np.concatenate([small_u, more_u]))
         assert tb_more > tb_small
+        # owners 0..299 held real counters beside the first-touch movers of that batch: their whole table
+        m = more_i < 300
+        exp = oracle.build_table(300, d, w, a, b, np.concatenate([small_i, more_i[m]]),
+                                 np.concatenate([small_u, more_u[m]]), None)
+        assert same(t.read_counters_device(0, 300).cpu().numpy().astype(np.float64), exp)
         t.reset()
         t.ingest(big_i, big_u)
         t.finalize()
