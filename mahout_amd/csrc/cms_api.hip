@@ -1057,15 +1057,14 @@ static int estimate_on(cms_handle* h, int64_t user_id, const int64_t* neighbor_i
     for (int64_t i = 0; i < m; ++i)
       if (rows[i] != urow) others.push_back(rows[i]);
     if ((rc = po_require_shapes(h, others.data(), (int64_t)others.size()))) return rc;
-    if ((rc = po_pair_cosines(h, d_rows + m, 1, d_rows, m, d_sims, ks))) return rc;
-    rc = po_estimate_preferences(h, urow, d_rows, d_sims, m, c.q.as<int64_t>(), q, use_capper, cap_min, cap_max,
-                                 c.o.as<float>(), ks);
+    rc = po_pair_cosines(h, d_rows + m, 1, d_rows, m, d_sims, ks);
   } else {
-    if ((rc = pair_cosines(h, urow, d_rows, m, d_sims, ks))) return rc;
-    rc = estimate_preferences(h, urow, d_rows, d_sims, m, c.q.as<int64_t>(), q, use_capper, cap_min, cap_max,
-                              c.o.as<float>(), ks);
+    rc = pair_cosines(h, urow, d_rows, m, d_sims, ks);
   }
   if (rc) return rc;
+  if ((rc = estimate_preferences(h, urow, d_rows, d_sims, m, c.q.as<int64_t>(), q, use_capper, cap_min, cap_max,
+                                 c.o.as<float>(), ks)))
+    return rc;
   CMS_HIP(hipMemcpyAsync(out, c.o.ptr, sizeof(float) * q, hipMemcpyDeviceToHost, st));
   CMS_HIP(hipStreamSynchronize(st));
   return CMS_OK;
@@ -1251,13 +1250,8 @@ int cms_point_query(cms_handle* h, int64_t id, int64_t key, double* out) {
   CMS_HIP(c.q.ensure(sizeof(int64_t)));
   CMS_HIP(c.o.ensure(sizeof(double)));
   CMS_HIP(hipMemcpyAsync(c.q.ptr, &key, sizeof(int64_t), hipMemcpyHostToDevice, c.stream));
-  if (h->per_owner) {
-    if ((rc = po_require_shapes(h, &row, 1))) return rc;
-    rc = po_point_queries(h, row, c.q.as<int64_t>(), 1, c.o.as<double>(), c.stream);
-  } else {
-    rc = point_queries(h, row, c.q.as<int64_t>(), 1, c.o.as<double>(), c.stream);
-  }
-  if (rc) return rc;
+  if (h->per_owner && (rc = po_require_shapes(h, &row, 1))) return rc;
+  if ((rc = point_queries(h, row, c.q.as<int64_t>(), 1, c.o.as<double>(), c.stream))) return rc;
   CMS_HIP(hipMemcpyAsync(out, c.o.ptr, sizeof(double), hipMemcpyDeviceToHost, c.stream));
   CMS_HIP(hipStreamSynchronize(c.stream));
   return CMS_OK;

@@ -32,6 +32,7 @@
 #include "cms_device.h"
 #include "cms_internal.h"
 #include "cms_mfma.h"
+#include "cms_ref.h"
 
 namespace cms {
 
@@ -232,12 +233,6 @@ __global__ void k_tile_limbs(const uint8_t* rowL, int64_t nrows, uint8_t* tileL)
 }
 
 // ------------------------------------------------------------- the kernel --
-
-__device__ __forceinline__ double java_min_d(double a, double b) {
-  if (a != a) return a;
-  if (a == 0.0 && b == 0.0 && signbit(b)) return b;
-  return (a <= b) ? a : b;
-}
 
 // LDS image of one 128 x 128-byte operand tile: row-major rows of 128 B, the
 // 16-B chunk index XOR-swizzled with (row >> 1) & 7 so that every
@@ -480,7 +475,7 @@ __global__ __launch_bounds__(256, MULTI ? 1 : 2) void k_cosine_tile(CosArgs a, c
                 acc[i][j][e] = 0;
               }
               const double den = __dmul_rn(sa, sb);
-              if (den != 0.0) mn[i][j][e] = java_min_d(mn[i][j][e], __ddiv_rn(valueAB, den));
+              if (den != 0.0) mn[i][j][e] = java_min(mn[i][j][e], __ddiv_rn(valueAB, den));
             }
           }
         }
@@ -498,13 +493,7 @@ __global__ __launch_bounds__(256, MULTI ? 1 : 2) void k_cosine_tile(CosArgs a, c
       for (int e = 0; e < 16; ++e) {
         const int64_t grow = row0 + wr * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
         if (grow >= a.q0 + a.qcount || gcol >= a.n) continue;
-        double rr = mn[i][j][e] == DBL_MAX ? __builtin_nan("") : mn[i][j][e];
-        if (rr == rr) {
-          if (a.weighted) rr = rr < 0.0 ? -1.0 : 1.0;  // scaleFactor 1 - 1/(0+1) = 0
-          if (rr < -1.0) rr = -1.0;
-          else if (rr > 1.0) rr = 1.0;
-        }
-        a.out[(grow - a.q0) * a.ldo + gcol] = rr;
+        a.out[(grow - a.q0) * a.ldo + gcol] = cosine_finish(mn[i][j][e], a.weighted);
       }
     }
 }

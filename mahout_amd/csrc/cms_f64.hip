@@ -23,6 +23,7 @@
 
 #include "cms_device.h"
 #include "cms_internal.h"
+#include "cms_ref.h"
 
 namespace cms {
 
@@ -97,9 +98,7 @@ __device__ double f64_cosine_cm(const double* tab, const double* nsqrt, int64_t 
     const double den = __dmul_rn(nsqrt[qa * depth + d], nsqrt[qb * depth + d]);
     if (den != 0.0) minc = java_min(minc, __ddiv_rn(ab, den));
   }
-  double r = minc == DBL_MAX ? __builtin_nan("") : minc;
-  if (r == r) r = normalize_weight(r, weighted);
-  return r;
+  return cosine_finish(minc, weighted);
 }
 
 // similarities of (q_row, rows[i]) into out[i]; an unknown row gives NaN
@@ -118,61 +117,6 @@ __global__ void k_f64_slab(const double* tab, const double* nsqrt, int depth, in
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t q = i / n, c = i - q * n;
     slab[i] = f64_cosine_cm(tab, nsqrt, q0 + q, c, depth, w, weighted);
-  }
-}
-
-// DoubleCountMinSketch.get(key) (:94-103) on fp64 counters
-__global__ void k_f64_point(const double* tab, HashParams hp, int64_t row, const int64_t* keys, int64_t m,
-                            double* out) {
-  const int64_t dw = (int64_t)hp.depth * hp.width;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t kp = reduce_key(keys[i]);
-    double est = DBL_MAX;
-    for (int d = 0; d < hp.depth; ++d) {
-      const double v = tab[row * dw + (int64_t)d * hp.width + bucket(hp, d, kp)];
-      if (v < est) est = v;
-    }
-    out[i] = est;
-  }
-}
-
-// doEstimatePreference (GenericUserBasedRecommender.java:134-184) on fp64
-// counters: the k_estimate loop with the point query read as doubles
-__global__ void k_f64_estimate(const double* tab, HashParams hp, int64_t user_row, const int64_t* nb_rows,
-                               const double* sims, int64_t m, const int64_t* items, int64_t q, int use_capper,
-                               float lo, float hi, float* out) {
-  const int64_t dw = (int64_t)hp.depth * hp.width;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < q; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t kp = reduce_key(items[i]);
-    uint32_t bk[CMS_MAX_DEPTH];
-    for (int d = 0; d < hp.depth; ++d) bk[d] = (uint32_t)d * hp.width + bucket(hp, d, kp);
-    double preference = 0.0, total = 0.0;
-    int count = 0;
-    for (int64_t j = 0; j < m; ++j) {
-      const int64_t r = nb_rows[j];
-      if (r == user_row) continue;
-      double est = DBL_MAX;
-      for (int d = 0; d < hp.depth; ++d) {
-        const double v = tab[r * dw + bk[d]];
-        if (v < est) est = v;
-      }
-      const float pref = (float)est;
-      if (pref == 0.0f) continue;
-      const double s = sims[j];
-      if (s != s) continue;
-      preference = __dadd_rn(preference, __dmul_rn(s, (double)pref));
-      total = __dadd_rn(total, s);
-      ++count;
-    }
-    float e = __builtin_nanf("");
-    if (count > 1) {
-      e = (float)__ddiv_rn(preference, total);
-      if (use_capper) {
-        if (e > hi) e = hi;
-        else if (e < lo) e = lo;
-      }
-    }
-    out[i] = e;
   }
 }
 
@@ -267,62 +211,8 @@ __global__ __launch_bounds__(kF64Threads) void k_po_f64_pairs(const int64_t* off
       }
       __syncthreads();
     }
-    if (threadIdx.x == 0) {
-      double r = s_min == DBL_MAX ? __builtin_nan("") : s_min;
-      if (r == r) r = normalize_weight(r, weighted);
-      out[t] = r;
-    }
+    if (threadIdx.x == 0) out[t] = cosine_finish(s_min, weighted);
     __syncthreads();
-  }
-}
-
-__global__ void k_po_f64_point(const PoShape* shp, const double* sk, HashParams hp, int64_t row, const int64_t* keys,
-                               int64_t m, double* out) {
-  const PoShape s = shp[row];
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t kp = reduce_key(keys[i]);
-    double est = DBL_MAX;
-    for (int d = 0; d < s.d; ++d) {
-      const double v = sk[s.soff + (int64_t)d * s.w + bucket_wb(hp, d, kp, (uint32_t)s.w, s.barrett)];
-      if (v < est) est = v;
-    }
-    out[i] = est;
-  }
-}
-
-__global__ void k_po_f64_estimate(const PoShape* shp, const double* sk, HashParams hp, int64_t user_row,
-                                  const int64_t* nb_rows, const double* sims, int64_t m, const int64_t* items,
-                                  int64_t q, int use_capper, float lo, float hi, float* out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < q; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t kp = reduce_key(items[i]);
-    double preference = 0.0, total = 0.0;
-    int count = 0;
-    for (int64_t j = 0; j < m; ++j) {
-      const int64_t r = nb_rows[j];
-      if (r == user_row) continue;
-      const PoShape s = shp[r];
-      double est = DBL_MAX;
-      for (int d = 0; d < s.d; ++d) {
-        const double v = sk[s.soff + (int64_t)d * s.w + bucket_wb(hp, d, kp, (uint32_t)s.w, s.barrett)];
-        if (v < est) est = v;
-      }
-      const float pref = (float)est;
-      if (pref == 0.0f) continue;
-      const double sim = sims[j];
-      if (sim != sim) continue;
-      preference = __dadd_rn(preference, __dmul_rn(sim, (double)pref));
-      total = __dadd_rn(total, sim);
-      ++count;
-    }
-    float e = __builtin_nanf("");
-    if (count > 1) {
-      e = (float)__ddiv_rn(preference, total);
-      if (use_capper) {
-        if (e > hi) e = hi;
-        else if (e < lo) e = lo;
-      }
-    }
-    out[i] = e;
   }
 }
 
@@ -425,23 +315,6 @@ int f64_slab(cms_handle* h, int64_t q0, int64_t qc, double* d_slab) {
   return CMS_OK;
 }
 
-int f64_point_queries(cms_handle* h, int64_t row, const int64_t* d_keys, int64_t m, double* d_out, hipStream_t s) {
-  if (m <= 0) return CMS_OK;
-  hipLaunchKernelGGL(k_f64_point, dim3(grid_for(m)), dim3(256), 0, s ? s : h->stream, h->d_t64, h->hp, row, d_keys, m, d_out);
-  CMS_HIP(hipGetLastError());
-  return CMS_OK;
-}
-
-int f64_estimate_preferences(cms_handle* h, int64_t user_row, const int64_t* d_nb_rows, const double* d_sims,
-                             int64_t m, const int64_t* d_items, int64_t q, int use_capper, float lo, float hi,
-                             float* d_out, hipStream_t s) {
-  if (q <= 0) return CMS_OK;
-  hipLaunchKernelGGL(k_f64_estimate, dim3(grid_for(q)), dim3(256), 0, s ? s : h->stream, h->d_t64, h->hp, user_row, d_nb_rows,
-                     d_sims, m, d_items, q, use_capper, lo, hi, d_out);
-  CMS_HIP(hipGetLastError());
-  return CMS_OK;
-}
-
 }  // namespace cms
 
 namespace cms {
@@ -485,23 +358,6 @@ int po_f64_pair_cosines(cms_handle* h, const int64_t* d_qrows, int64_t nq, const
                      h->po_kp.as<uint64_t>(), h->po_v64.as<double>(), h->po_shape.as<PoShape>(), h->po_sk.as<double>(),
                      h->po_nsq.as<double>(), h->hp, d_qrows, nq, d_crows, m, h->po_scratch.as<double>(),
                      (int64_t)std::max(1, h->po_max_w), (int)(h->p.weighting == CMS_WEIGHTED), d_out);
-  CMS_HIP(hipGetLastError());
-  return CMS_OK;
-}
-
-int po_f64_point_queries(cms_handle* h, int64_t row, const int64_t* d_keys, int64_t m, double* d_out, hipStream_t s) {
-  hipLaunchKernelGGL(k_po_f64_point, dim3(grid_for(m)), dim3(256), 0, s ? s : h->stream, h->po_shape.as<PoShape>(),
-                     h->po_sk.as<double>(), h->hp, row, d_keys, m, d_out);
-  CMS_HIP(hipGetLastError());
-  return CMS_OK;
-}
-
-int po_f64_estimate_preferences(cms_handle* h, int64_t user_row, const int64_t* d_nb_rows, const double* d_sims,
-                                int64_t m, const int64_t* d_items, int64_t q, int use_capper, float lo, float hi,
-                                float* d_out, hipStream_t s) {
-  hipLaunchKernelGGL(k_po_f64_estimate, dim3(grid_for(q)), dim3(256), 0, s ? s : h->stream, h->po_shape.as<PoShape>(),
-                     h->po_sk.as<double>(), h->hp, user_row, d_nb_rows, d_sims, m, d_items, q, use_capper, lo, hi,
-                     d_out);
   CMS_HIP(hipGetLastError());
   return CMS_OK;
 }

@@ -548,6 +548,8 @@ int partition_to_spans(cms_handle* h, const int64_t* d_row, const int64_t* d_key
 // stream is never timed)
 int pair_cosines(cms_handle* h, int64_t q_row, const int64_t* d_rows, int64_t m, double* d_out,
                  hipStream_t s = nullptr);
+// point queries and estimates in the handle's mode (fixed or per-owner shapes,
+// u32 or fp64 counters: the accessors of cms_ref.h)
 int point_queries(cms_handle* h, int64_t row, const int64_t* d_keys, int64_t m, double* d_out, hipStream_t s = nullptr);
 int pair_cosines_many(cms_handle* h, const int64_t* d_qrows, const int64_t* d_rows, int64_t m, double* d_out,
                       hipStream_t s);
@@ -628,11 +630,6 @@ int po_finalize(cms_handle* h);
 // similarities of (qrows[i / m], crows[i % m]) into out[i] (crows null: identity)
 int po_pair_cosines(cms_handle* h, const int64_t* d_qrows, int64_t nq, const int64_t* d_crows, int64_t m, double* d_out,
                     hipStream_t s = nullptr);
-int po_point_queries(cms_handle* h, int64_t row, const int64_t* d_keys, int64_t m, double* d_out,
-                     hipStream_t s = nullptr);
-int po_estimate_preferences(cms_handle* h, int64_t user_row, const int64_t* d_nb_rows, const double* d_sims, int64_t m,
-                            const int64_t* d_items, int64_t q, int use_capper, float lo, float hi, float* d_out,
-                            hipStream_t s = nullptr);
 int po_top_k_rows(cms_handle* h, int64_t row_begin, int64_t row_count, int32_t k, int64_t* d_ids, double* d_scores,
                   int32_t* d_counts);
 // shape check of every owner in rows (all owners when rows is null)
@@ -658,17 +655,9 @@ int po_f64_load(cms_handle* h, const int64_t* d_key, const float* d_val, int64_t
 int po_f64_finalize(cms_handle* h, int64_t total_counters, int64_t total_rows);
 int po_f64_pair_cosines(cms_handle* h, const int64_t* d_qrows, int64_t nq, const int64_t* d_crows, int64_t m,
                         double* d_out, hipStream_t s);
-int po_f64_point_queries(cms_handle* h, int64_t row, const int64_t* d_keys, int64_t m, double* d_out, hipStream_t s);
-int po_f64_estimate_preferences(cms_handle* h, int64_t user_row, const int64_t* d_nb_rows, const double* d_sims,
-                                int64_t m, const int64_t* d_items, int64_t q, int use_capper, float lo, float hi,
-                                float* d_out, hipStream_t s);
 int f64_norms(cms_handle* h);
 int f64_pair_cosines(cms_handle* h, int64_t q_row, const int64_t* d_rows, int64_t m, double* d_out, hipStream_t s);
 int f64_slab(cms_handle* h, int64_t q0, int64_t qc, double* d_slab);
-int f64_point_queries(cms_handle* h, int64_t row, const int64_t* d_keys, int64_t m, double* d_out, hipStream_t s);
-int f64_estimate_preferences(cms_handle* h, int64_t user_row, const int64_t* d_nb_rows, const double* d_sims,
-                             int64_t m, const int64_t* d_items, int64_t q, int use_capper, float lo, float hi,
-                             float* d_out, hipStream_t s);
 // ---- cms_output.cpp ----
 int java_double_to_string(double v, char* out, int cap);
 // cms_recommend.cpp: GenericUserBasedRecommender's host logic (FastIDSet

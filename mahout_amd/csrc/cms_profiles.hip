@@ -29,6 +29,7 @@
 
 #include "cms_device.h"
 #include "cms_internal.h"
+#include "cms_ref.h"
 
 namespace cms {
 
@@ -202,12 +203,6 @@ struct PoPairArgs {
   uint32_t* no_rows = nullptr;  // pairs that needed a global bucket row without scratch (a host error)
 };
 
-__device__ __forceinline__ uint64_t po_wave_sum(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = sat_add(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // Open-addressed LDS table of at most 256 distinct buckets: keys (bucket + 1)
 // at lds[0, kPoTab), counts at lds[kPoTab, 2 kPoTab); the slot of bucket j.
 constexpr int kPoTab = 512;
@@ -223,7 +218,7 @@ __device__ __forceinline__ uint32_t po_tab_insert(uint32_t* lds, uint32_t j) {
 // Sum over the NT threads of a block (every thread gets it).
 template <int NT>
 __device__ __forceinline__ uint64_t po_block_sum(uint64_t v, unsigned long long* red) {
-  v = po_wave_sum(v);
+  v = wave_sum_u64_sat(v);
   if (NT == 64) return v;
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -392,11 +387,9 @@ __global__ __launch_bounds__(NT) void k_po_pairs(PoPairArgs a, HashParams hp) {
       }
       if (den != 0.0) minc = java_min(minc, __ddiv_rn(valueAB, den));
     }
-    if (lane == 0) {
-      double r = (minc == DBL_MAX) ? __builtin_nan("") : minc;
-      if (r == r) r = normalize_weight(r, a.weighted);
-      a.out[a.plist ? (u1 - a.q0) * a.ldo + u2 : a.ldo > 0 ? (t / a.m) * a.ldo + u2 : t] = r;
-    }
+    if (lane == 0)
+      a.out[a.plist ? (u1 - a.q0) * a.ldo + u2 : a.ldo > 0 ? (t / a.m) * a.ldo + u2 : t] =
+          cosine_finish(minc, a.weighted);
   }
 }
 
@@ -547,7 +540,7 @@ __global__ __launch_bounds__(64 * kPoGroupWaves) void k_po_group_pairs(PoAllArgs
           a2 = sat_add(a2, (uint64_t)cc * cc);
         }
       }
-      a2 = po_wave_sum(a2);
+      a2 = wave_sum_u64_sat(a2);
       if (member) {
         if (a2 < (1ULL << 53) && a.norm[roff + r] < (1ULL << 53)) {
           const double den = __dmul_rn(__dsqrt_rn((double)a2), a.nsq[roff + r]);
@@ -558,8 +551,7 @@ __global__ __launch_bounds__(64 * kPoGroupWaves) void k_po_group_pairs(PoAllArgs
       }
     }
     if (member) {
-      double res = minc == DBL_MAX ? __builtin_nan("") : minc;
-      if (res == res) res = normalize_weight(res, a.weighted);
+      double res = cosine_finish(minc, a.weighted);
       if (inexact) {  // k_po_pairs replays the reference's sequential loop
         res = __builtin_nan("");
         const uint32_t slot = atomicAdd(a.redo_cnt, 1u);
@@ -623,7 +615,7 @@ __global__ __launch_bounds__(kPoBigThreads) void k_po_bigq(PoBigArgs a, HashPara
       const uint32_t x = lds[r * w + j];
       a2 = sat_add(a2, (uint64_t)x * x);
     }
-    a2 = po_wave_sum(a2);
+    a2 = wave_sum_u64_sat(a2);
     if ((tid & 63) == 0 && a2) atomicAdd(&s_a2[r], (unsigned long long)a2);
   }
   __syncthreads();
@@ -658,8 +650,7 @@ __global__ __launch_bounds__(kPoBigThreads) void k_po_bigq(PoBigArgs a, HashPara
       }
     }
     if (!live || part != 0) continue;
-    double res = minc == DBL_MAX ? __builtin_nan("") : minc;
-    if (res == res) res = normalize_weight(res, a.weighted);
+    double res = cosine_finish(minc, a.weighted);
     if (inexact) {
       res = __builtin_nan("");
       const uint32_t slot = atomicAdd(a.redo_cnt, 1u);
@@ -848,59 +839,6 @@ __global__ __launch_bounds__(64 * kPoBoundWaves) void k_po_wide_bound(PoBoundArg
   } else {
     po_append(a, 0, keep && !global_rows, e);
     po_append(a, 1, keep && global_rows, e);
-  }
-}
-
-// DoubleCountMinSketch.get(key) (:94-103) of the owner's own sketch.
-__global__ void k_po_point(const PoShape* shp, const uint32_t* sk, HashParams hp, int64_t row, const int64_t* keys,
-                           int64_t m, double* out) {
-  const PoShape s = shp[row];
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t kp = reduce_key(keys[i]);
-    double est = DBL_MAX;
-    for (int d = 0; d < s.d; ++d) {
-      const double v = (double)sk[s.soff + (int64_t)d * s.w + bucket_wbq(hp, d, kp, (uint32_t)s.w, s.barrett)];
-      if (v < est) est = v;
-    }
-    out[i] = ldexp(est, -hp.frac_bits);
-  }
-}
-
-// doEstimatePreference with the point query of each neighbour's own sketch
-// (GenericUserBasedRecommender.java:134-184), as k_estimate for fixed shapes.
-__global__ void k_po_estimate(const PoShape* shp, const uint32_t* sk, HashParams hp, int64_t user_row,
-                              const int64_t* nb_rows, const double* sims, int64_t m, const int64_t* items, int64_t q,
-                              int use_capper, float lo, float hi, float* out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < q; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t kp = reduce_key(items[i]);
-    double preference = 0.0, total = 0.0;
-    int count = 0;
-    for (int64_t j = 0; j < m; ++j) {
-      const int64_t r = nb_rows[j];
-      if (r == user_row) continue;
-      const PoShape s = shp[r];
-      double est = DBL_MAX;
-      for (int d = 0; d < s.d; ++d) {
-        const double v = (double)sk[s.soff + (int64_t)d * s.w + bucket_wbq(hp, d, kp, (uint32_t)s.w, s.barrett)];
-        if (v < est) est = v;
-      }
-      const float pref = (float)ldexp(est, -hp.frac_bits);
-      if (pref == 0.0f) continue;
-      const double sim = sims[j];
-      if (sim != sim) continue;
-      preference = __dadd_rn(preference, __dmul_rn(sim, (double)pref));
-      total = __dadd_rn(total, sim);
-      ++count;
-    }
-    float e = __builtin_nanf("");
-    if (count > 1) {
-      e = (float)__ddiv_rn(preference, total);
-      if (use_capper) {
-        if (e > hi) e = hi;
-        else if (e < lo) e = lo;
-      }
-    }
-    out[i] = e;
   }
 }
 
@@ -1195,28 +1133,6 @@ int po_pair_cosines(cms_handle* h, const int64_t* d_qrows, int64_t nq, const int
   TimedScope ts(h, "po_pair_cosine", s == nullptr);
   hipLaunchKernelGGL(k_po_pairs<kPoThreads>, dim3(grid_for(nq * m, wide ? kPoGridWide : kPoGrid)), dim3(kPoThreads), 0,
                      s ? s : h->stream, a, h->hp);
-  CMS_HIP(hipGetLastError());
-  return CMS_OK;
-}
-
-int po_point_queries(cms_handle* h, int64_t row, const int64_t* d_keys, int64_t m, double* d_out, hipStream_t s) {
-  if (m <= 0) return CMS_OK;
-  if (h->f64) return po_f64_point_queries(h, row, d_keys, m, d_out, s);
-  hipLaunchKernelGGL(k_po_point, dim3(grid_for((m + 255) / 256, 4096)), dim3(256), 0, s ? s : h->stream,
-                     h->po_shape.as<PoShape>(), h->po_sk.as<uint32_t>(), h->hp, row, d_keys, m, d_out);
-  CMS_HIP(hipGetLastError());
-  return CMS_OK;
-}
-
-int po_estimate_preferences(cms_handle* h, int64_t user_row, const int64_t* d_nb_rows, const double* d_sims, int64_t m,
-                            const int64_t* d_items, int64_t q, int use_capper, float lo, float hi, float* d_out,
-                            hipStream_t s) {
-  if (q <= 0) return CMS_OK;
-  if (h->f64)
-    return po_f64_estimate_preferences(h, user_row, d_nb_rows, d_sims, m, d_items, q, use_capper, lo, hi, d_out, s);
-  hipLaunchKernelGGL(k_po_estimate, dim3(grid_for((q + 255) / 256, 4096)), dim3(256), 0, s ? s : h->stream,
-                     h->po_shape.as<PoShape>(), h->po_sk.as<uint32_t>(), h->hp, user_row, d_nb_rows, d_sims, m,
-                     d_items, q, use_capper, lo, hi, d_out);
   CMS_HIP(hipGetLastError());
   return CMS_OK;
 }

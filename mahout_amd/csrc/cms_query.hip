@@ -19,6 +19,7 @@
 
 #include "cms_device.h"
 #include "cms_internal.h"
+#include "cms_ref.h"
 
 namespace cms {
 
@@ -105,11 +106,7 @@ __global__ __launch_bounds__(256) void k_pair_cosine(TableView tv, const uint64_
     }
     if (den != 0.0) minc = java_min(minc, __ddiv_rn(valueAB, den));
   }
-  if (threadIdx.x == 0) {
-    double r = (minc == DBL_MAX) ? __builtin_nan("") : minc;
-    if (r == r) r = normalize_weight(r, weighted);
-    out[t] = r;
-  }
+  if (threadIdx.x == 0) out[t] = cosine_finish(minc, weighted);
 }
 
 int pair_cosines(cms_handle* h, int64_t q_row, const int64_t* d_rows, int64_t m, double* d_out, hipStream_t s) {
@@ -136,139 +133,95 @@ int pair_cosines_many(cms_handle* h, const int64_t* d_qrows, const int64_t* d_ro
   return CMS_OK;
 }
 
-// DoubleCountMinSketch.get(key) (:94-103): min over rows, from Double.MAX_VALUE.
-__global__ void k_point_query(TableView tv, HashParams hp, int64_t row, const int64_t* keys, int64_t m,
-                              double* out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
-    uint64_t kp = reduce_key(keys[i]);
-    double est = DBL_MAX;
-    for (int d = 0; d < hp.depth; ++d) {
-      double v = (double)tv.get(row, (int64_t)d * hp.width + bucket(hp, d, kp));
-      if (v < est) est = v;
+// DoubleCountMinSketch.get(key) (:94-103) of one owner for m keys, one thread
+// per key, in the handle's mode (its counter accessor, cms_ref.h).
+template <class Acc>
+__global__ void k_point_query(Acc acc, int64_t row, const int64_t* keys, int64_t m, double* out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = sketch_get(acc, row, reduce_key(keys[i]));
+}
+
+// The users of one k_estimate launch.  A batch: candidate i belongs to user
+// item_user[i], whose row is user_rows[u] and whose neighbourhood (rows and
+// similarities, in the caller's order) is nb_rows / sims [nb_off[u],
+// nb_off[u + 1]).  One user (item_user null): user_row and nb_rows / sims
+// [0, m), here by value.
+struct Neighbourhoods {
+  const int64_t* user_rows;
+  const int64_t* nb_off;
+  const int32_t* item_user;
+  int64_t user_row, m;
+};
+
+// doEstimatePreference (estimate_one, cms_ref.h), one thread per candidate
+// item.  BATCH = nh is a batch: compiled apart, so the one-user launch keeps
+// its smaller register file.
+template <class Acc, bool BATCH>
+__global__ void k_estimate(Acc acc, Neighbourhoods nh, const int64_t* nb_rows, const double* sims,
+                           const int64_t* items, int64_t q, int use_capper, float lo, float hi, float* out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < q; i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t user_row = nh.user_row, j0 = 0, m = nh.m;
+    if (BATCH) {
+      const int32_t u = nh.item_user[i];
+      user_row = nh.user_rows[u];
+      j0 = nh.nb_off[u];
+      m = nh.nb_off[u + 1] - j0;
     }
-    out[i] = ldexp(est, -hp.frac_bits);
+    out[i] = estimate_one(acc, user_row, nb_rows + j0, sims + j0, m, reduce_key(items[i]), use_capper, lo, hi);
   }
 }
 
-// GenericUserBasedRecommender.doEstimatePreference with the CosineCM point
-// query (GenericUserBasedRecommender.java:134-184), one thread per item, the
-// neighbourhood walked in the caller's order so the fp64 sums round as in Java:
-// pref = (float) get(item) of the neighbour's sketch (0 -> no data point),
-// sim = userSimilarity(user, neighbour) (NaN skipped), preference += sim*pref,
-// total += sim; < 2 points -> NaN; (float)(preference/total); then the
-// EstimatedPreferenceCapper clamp when enabled.
-__global__ void k_estimate(TableView tv, HashParams hp, int64_t user_row, const int64_t* nb_rows,
-                           const double* sims, int64_t m, const int64_t* items, int64_t q, int use_capper, float lo,
-                           float hi, float* out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < q; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t kp = reduce_key(items[i]);
-    uint32_t bk[CMS_MAX_DEPTH];
-    for (int d = 0; d < hp.depth; ++d) bk[d] = (uint32_t)d * hp.width + bucket(hp, d, kp);
-    double preference = 0.0, total = 0.0;
-    int count = 0;
-    for (int64_t j = 0; j < m; ++j) {
-      const int64_t r = nb_rows[j];
-      if (r == user_row) continue;
-      double est = DBL_MAX;
-      for (int d = 0; d < hp.depth; ++d) {
-        const double v = (double)tv.get(r, bk[d]);
-        if (v < est) est = v;
-      }
-      const float pref = (float)ldexp(est, -hp.frac_bits);
-      if (pref == 0.0f) continue;
-      const double s = sims[j];
-      if (s != s) continue;
-      preference = __dadd_rn(preference, __dmul_rn(s, (double)pref));
-      total = __dadd_rn(total, s);
-      ++count;
-    }
-    float e = __builtin_nanf("");
-    if (count > 1) {
-      e = (float)__ddiv_rn(preference, total);
-      if (use_capper) {
-        if (e > hi) e = hi;
-        else if (e < lo) e = lo;
-      }
-    }
-    out[i] = e;
+// f(acc) with the counter accessor of the handle's mode: the one place that
+// tells fixed from per-owner shapes and u32 from fp64 counters for the point
+// queries and estimates.
+template <class F>
+static int with_accessor(cms_handle* h, F&& f) {
+  if (h->per_owner) {
+    const PoShape* shp = h->po_shape.as<PoShape>();
+    return h->f64 ? f(PoF64{shp, h->po_sk.as<double>(), h->hp}) : f(PoU32{shp, h->po_sk.as<uint32_t>(), h->hp});
   }
+  return h->f64 ? f(FixedF64{h->d_t64, h->hp}) : f(FixedU32{h->tview(), h->hp});
+}
+
+static int launch_estimate(cms_handle* h, const Neighbourhoods& nh, const int64_t* d_nb_rows, const double* d_sims,
+                           const int64_t* d_items, int64_t q, int use_capper, float lo, float hi, float* d_out,
+                           int64_t grid_cap, hipStream_t s) {
+  if (q <= 0) return CMS_OK;
+  const unsigned grid = (unsigned)std::min<int64_t>((q + 255) / 256, grid_cap);
+  return with_accessor(h, [&](auto acc) {
+    using Acc = decltype(acc);
+    auto* kernel = nh.item_user ? k_estimate<Acc, true> : k_estimate<Acc, false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s ? s : h->stream, acc, nh, d_nb_rows, d_sims, d_items, q,
+                       use_capper, lo, hi, d_out);
+    CMS_HIP(hipGetLastError());
+    return (int)CMS_OK;
+  });
 }
 
 int estimate_preferences(cms_handle* h, int64_t user_row, const int64_t* d_nb_rows, const double* d_sims, int64_t m,
                          const int64_t* d_items, int64_t q, int use_capper, float lo, float hi, float* d_out,
                          hipStream_t s) {
-  if (q <= 0) return CMS_OK;
-  if (h->f64)
-    return f64_estimate_preferences(h, user_row, d_nb_rows, d_sims, m, d_items, q, use_capper, lo, hi, d_out, s);
-  unsigned grid = (unsigned)std::min<int64_t>((q + 255) / 256, 4096);
-  hipLaunchKernelGGL(k_estimate, dim3(grid), dim3(256), 0, s ? s : h->stream, h->tview(), h->hp, user_row, d_nb_rows, d_sims,
-                     m, d_items, q, use_capper, lo, hi, d_out);
-  CMS_HIP(hipGetLastError());
-  return CMS_OK;
-}
-
-// k_estimate for many users in one launch: candidate i belongs to user
-// item_user[i], whose neighbourhood (rows and similarities, in the caller's
-// order) is nb_rows / sims [nb_off[u], nb_off[u + 1]).  Each candidate's
-// arithmetic is exactly k_estimate's.
-__global__ void k_estimate_batch(TableView tv, HashParams hp, const int64_t* user_rows, const int64_t* nb_off,
-                                 const int64_t* nb_rows, const double* sims, const int32_t* item_user,
-                                 const int64_t* items, int64_t q, int use_capper, float lo, float hi, float* out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < q; i += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t u = item_user[i];
-    const int64_t user_row = user_rows[u];
-    const uint64_t kp = reduce_key(items[i]);
-    uint32_t bk[CMS_MAX_DEPTH];
-    for (int d = 0; d < hp.depth; ++d) bk[d] = (uint32_t)d * hp.width + bucket(hp, d, kp);
-    double preference = 0.0, total = 0.0;
-    int count = 0;
-    for (int64_t j = nb_off[u]; j < nb_off[u + 1]; ++j) {
-      const int64_t r = nb_rows[j];
-      if (r == user_row) continue;
-      double est = DBL_MAX;
-      for (int d = 0; d < hp.depth; ++d) {
-        const double v = (double)tv.get(r, bk[d]);
-        if (v < est) est = v;
-      }
-      const float pref = (float)ldexp(est, -hp.frac_bits);
-      if (pref == 0.0f) continue;
-      const double s = sims[j];
-      if (s != s) continue;
-      preference = __dadd_rn(preference, __dmul_rn(s, (double)pref));
-      total = __dadd_rn(total, s);
-      ++count;
-    }
-    float e = __builtin_nanf("");
-    if (count > 1) {
-      e = (float)__ddiv_rn(preference, total);
-      if (use_capper) {
-        if (e > hi) e = hi;
-        else if (e < lo) e = lo;
-      }
-    }
-    out[i] = e;
-  }
+  return launch_estimate(h, Neighbourhoods{nullptr, nullptr, nullptr, user_row, m}, d_nb_rows, d_sims, d_items, q,
+                         use_capper, lo, hi, d_out, h->f64 ? 8192 : 4096, s);
 }
 
 int estimate_preferences_batch(cms_handle* h, const int64_t* d_user_rows, const int64_t* d_nb_off,
                                const int64_t* d_nb_rows, const double* d_sims, const int32_t* d_item_user,
                                const int64_t* d_items, int64_t q, int use_capper, float lo, float hi, float* d_out,
                                hipStream_t s) {
-  if (q <= 0) return CMS_OK;
-  unsigned grid = (unsigned)std::min<int64_t>((q + 255) / 256, 8192);
-  hipLaunchKernelGGL(k_estimate_batch, dim3(grid), dim3(256), 0, s ? s : h->stream, h->tview(), h->hp, d_user_rows,
-                     d_nb_off, d_nb_rows, d_sims, d_item_user, d_items, q, use_capper, lo, hi, d_out);
-  CMS_HIP(hipGetLastError());
-  return CMS_OK;
+  return launch_estimate(h, Neighbourhoods{d_user_rows, d_nb_off, d_item_user, 0, 0}, d_nb_rows, d_sims, d_items, q,
+                         use_capper, lo, hi, d_out, 8192, s);
 }
 
 int point_queries(cms_handle* h, int64_t row, const int64_t* d_keys, int64_t m, double* d_out, hipStream_t s) {
   if (m <= 0) return CMS_OK;
-  if (h->f64) return f64_point_queries(h, row, d_keys, m, d_out, s);
-  unsigned grid = (unsigned)std::min<int64_t>((m + 255) / 256, 4096);
-  hipLaunchKernelGGL(k_point_query, dim3(grid), dim3(256), 0, s ? s : h->stream, h->tview(), h->hp, row, d_keys, m, d_out);
-  CMS_HIP(hipGetLastError());
-  return CMS_OK;
+  const unsigned grid = (unsigned)std::min<int64_t>((m + 255) / 256, h->f64 ? 8192 : 4096);
+  return with_accessor(h, [&](auto acc) {
+    hipLaunchKernelGGL(k_point_query<decltype(acc)>, dim3(grid), dim3(256), 0, s ? s : h->stream, acc, row, d_keys, m,
+                       d_out);
+    CMS_HIP(hipGetLastError());
+    return (int)CMS_OK;
+  });
 }
 
 }  // namespace cms

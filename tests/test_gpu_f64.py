@@ -160,6 +160,51 @@ def test_f64_per_owner_shapes_bit_exact(oracle, kind):
         assert ids.tolist() == eids.tolist() and same(scs, escs)
 
 
+def test_f64_per_owner_estimate_preferences(oracle):
+    """doEstimatePreference (`GenericUserBasedRecommender.java:134-184`) on
+    per-owner shapes with fp64 counters: each neighbour's point query comes from
+    its own sketch at its own shape, cast to float; the user's own row is
+    skipped; (2.0, 4.0) caps.  The neighbours have five distinct (w, d) shapes."""
+    from mahout_amd.synth import movielens_like
+    users, items, _ = movielens_like(40, 120, 900, seed=5, min_per_user=5)
+    uid = np.unique(users)
+    rows = np.searchsorted(uid, users)
+    order = np.lexsort((items, rows))
+    rows, items = rows[order], items[order]
+    vals = np.round(np.random.Generator(np.random.PCG64(8)).uniform(0.5, 5.0, rows.size), 1).astype(np.float32)
+    off, keys, v = to_csr(rows, items, uid.size, vals)
+    a, b = oracle.hash_params(42, 32)
+    user, nb, capper = 4, [7, 4, 11, 30, 2, 19], (2.0, 4.0)
+    its = np.unique(keys)[:48]
+    with SketchTable(uid.size, seed=42, owner_ids=uid, per_owner=True, counters="f64") as t:
+        t.ingest_csr(off, keys, v)
+        t.configure_owner_shapes(1.0, 120)
+        t.finalize()
+        w, d = t.owner_shapes()[2:]
+        got = t.estimate_preferences(int(uid[user]), uid[nb], its, capper=capper)
+    others = [r for r in nb if r != user]
+    own = {r: oracle.export_profile(off, keys, v, r, int(w[r]), int(d[r]), a, b) for r in others}
+    sim = {r: oracle.per_owner_similarity(off, keys, v, (w, d), a, b, user, r) for r in others}
+    exp, uncapped = [], []
+    for it in its:
+        pref_sum = tot = 0.0
+        cnt = 0
+        for r in others:
+            p = np.float32(oracle.sketch_get(own[r], a, b, int(it)))
+            if p == 0 or np.isnan(sim[r]):
+                continue
+            pref_sum += sim[r] * float(p)
+            tot += sim[r]
+            cnt += 1
+        e = np.float32(pref_sum / tot) if cnt > 1 else np.float32(np.nan)
+        uncapped.append(e)
+        exp.append(np.float32(min(max(e, capper[0]), capper[1])) if cnt > 1 else e)
+    exp, uncapped = np.array(exp, np.float32), np.array(uncapped, np.float32)
+    assert np.isnan(exp).any() and np.isfinite(exp).any() and (uncapped < capper[0]).any()
+    assert len({(int(w[r]), int(d[r])) for r in nb}) > 1
+    assert same(got, exp)
+
+
 @pytest.mark.parametrize("per_owner", [False, True])
 def test_taste_mirror_float_datamodel(oracle, per_owner):
     """taste.CosineCM over a float-rated DataModel whose preferences the u32
