@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void k_row_bound_values(const int64_t* lo_, co
 
 // An owner of a fresh build whose every counter is provably below 2^8 (its
 // mass bound) and whose keys fit the register cache: built whole in LDS by
-// k_build_nibbles / k_build_bytes (not by k_build_rows).
+// k_build_lists / k_build_nibbles / k_build_bytes (not by k_build_rows).
 constexpr int64_t kByteKeys = 64 * kKeyRegs;  // one wave's register cache (k_build_nibbles)
 __device__ __forceinline__ bool byte_class(int32_t slot, int64_t nkeys, uint64_t bound) {
   return slot < 0 && nkeys <= kByteKeys && bound < 256;
@@ -1116,12 +1116,15 @@ __device__ __forceinline__ void nib_owner(
     int64_t row, uint32_t* lds, const int64_t* lo_, const int64_t* hi_, const Keys& keys, const float* vals,
     const HashParams& hp, const int32_t* row_hot, const uint64_t* bound, const TableView& tv, int32_t* hidx_w,
     uint32_t* cbound, uint64_t* row_mass, uint64_t* norm, uint32_t* rowmax, uint32_t* flags, int32_t* redo,
-    uint32_t* redo_cnt, int bit_keys, int crumb_keys, int list_keys) {
+    uint32_t* redo_cnt, int bit_keys, int crumb_keys, int list_keys, int lists_done) {
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
   const int64_t lo = lo_[row], hi = hi_[row];
   if (row_hot[row] >= 0 || !byte_class(tv.hidx[row], hi - lo, bound[row])) return;
   const int w = (int)hp.width;
+  // lists_done: k_build_lists has built the list rows
+  if (lists_done && nib_list_row(hi - lo, w, hp.depth, vals != nullptr, hp.frac_bits, bit_keys, crumb_keys, list_keys))
+    return;
   uint64_t kp[kKeyRegs];
   uint32_t ik[kKeyRegs];
   uint32_t mass = 0;
@@ -1220,12 +1223,223 @@ __global__ __launch_bounds__(64 * kNibWaves) __attribute__((amdgpu_waves_per_eu(
     const int64_t* lo_, const int64_t* hi_, Keys keys, const float* vals, int64_t nrows, HashParams hp,
     const int32_t* row_hot, const uint64_t* bound, TableView tv, int32_t* hidx_w, uint32_t* cbound, uint64_t* row_mass,
     uint64_t* norm, uint32_t* rowmax, uint32_t* flags, int32_t* redo, uint32_t* redo_cnt, int bit_keys,
-    int crumb_keys, int list_keys) {
+    int crumb_keys, int list_keys, int lists_done) {
   extern __shared__ __align__(16) uint32_t lds[];  // [kNibWaves][w / 8] words: one sketch row of nibbles per wave
   const int64_t nw = (int64_t)gridDim.x * kNibWaves;
   for (int64_t row = (int64_t)blockIdx.x * kNibWaves + (threadIdx.x >> 6); row < nrows; row += nw)
     nib_owner<SV>(row, lds, lo_, hi_, keys, vals, hp, row_hot, bound, tv, hidx_w, cbound, row_mass, norm, rowmax, flags,
-                  redo, redo_cnt, bit_keys, crumb_keys, list_keys);
+                  redo, redo_cnt, bit_keys, crumb_keys, list_keys, lists_done);
+}
+
+// The byte-class owners that nib_list_row makes list rows, on a fresh build
+// with unit increments at a power-of-two width (hp.fastq) and depth D: what
+// nib_owner gives them -- [0] = m, the [d][m] entries in key order, the norms
+// and the maximum from 4-bit counts in the wave's LDS slot, ~row to
+// k_build_bytes when a counter passes 15 -- without the generic kernel's
+// forms, weights and escalation.  Each key is hashed once for all D rows (one
+// fp64 conversion, bucket_q's usual route on constants in scalar registers;
+// the rare other routes repeat the key through bucket()), its entries
+// stored as they are produced and kept packed two to a register for the row
+// passes, which issue all of a sketch row's adds before they read an old
+// counter (one LDS wait per sketch row) and store zero to the words they
+// added into (the slot is zeroed whole once per wave).  The grid is resident
+// and wave g takes rows g, g + G, ...: the next owner's spans are loaded
+// before the current owner's hashes and its first 64 keys before the row
+// passes, so the two dependent global round trips overlap work.  SV is
+// unused (a list row has no dense stores); it keeps the name in line with
+// the other build kernels.
+// Wave-wide sum and maximum by DPP row operations: six VALU instructions and
+// a v_readlane, against six LDS round trips (ds_bpermute) of the __shfl_xor
+// form.  Quads, half rows and rows of 16 lanes fold in place, row_bcast15
+// carries rows 0 and 2 into rows 1 and 3, row_bcast31 rows 0-1 into rows 2-3:
+// lane 63 holds the result.
+template <typename F>
+__device__ __forceinline__ uint32_t wave_fold_dpp(uint32_t v, F f) {
+  v = f(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
+  v = f(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
+  v = f(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true));  // row_half_mirror
+  v = f(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true));  // row_mirror
+  v = f(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false)); // row_bcast15 into rows 1, 3 (0 elsewhere)
+  v = f(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false)); // row_bcast31 into rows 2, 3
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// k_build_lists' row passes for an owner of NS live key slots (the slots
+// below the last are full): the D sketch rows counted one after another as
+// 4-bit counters in the wave's slot.  A lane past the owner's last key adds 0
+// to word 0 (its packed buckets are 0), so no add sits under a branch and the
+// row's adds are all in flight before the first old counter is read.  Returns
+// whether a counter passed 15 (the owner then ends: wave-uniform).
+template <int D, int NS>
+__device__ __forceinline__ bool list_rows(uint32_t* slot, const uint32_t (&pk)[kKeyRegs][(D + 1) / 2], int lane,
+                                          int m, uint32_t (&sq)[3], uint32_t& vmax) {
+  const uint32_t tail = lane + 64 * (NS - 1) < m ? 1u : 0u;  // the last slot's lane holds a key
+  bool ovf = false;
+#pragma unroll
+  for (int r = 0; r < D; ++r) {
+    uint32_t c[NS], old[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      c[k] = (pk[k][r >> 1] >> ((r & 1) << 4)) & 0xFFFFu;
+      old[k] = atomicAdd(&slot[c[k] >> 3], (k < NS - 1 ? 1u : tail) << ((c[k] & 7u) << 2));
+    }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      const uint32_t live = k < NS - 1 ? 1u : tail;
+      const uint32_t o = (old[k] >> ((c[k] & 7u) << 2)) & 15u;
+      const uint32_t nv = (o + 1u) * live;
+      ovf |= nv > 15u;  // the add carried into the next counter
+      sq[r >> 1] += ((2u * o + 1u) * live) << ((r & 1) << 4);  // 2 c + 1 per unit add: telescopes to the exact sum of squares
+      vmax = max(vmax, nv);
+      // zero to just the words added into, after every lane's add of this row
+      // (one wave's LDS operations execute in order): 0.87 ms alone against
+      // 1.14 ms with the slot zeroed whole by 16-B stores before every row
+      slot[c[k] >> 3] = 0u;
+    }
+    if (__ballot(ovf)) return true;
+  }
+  return false;
+}
+
+template <int SV, int D>
+__global__ __launch_bounds__(64 * kNibWaves) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_build_lists(
+    const int64_t* lo_, const int64_t* hi_, Keys keys, int64_t nrows, HashParams hp, const int32_t* row_hot,
+    const uint64_t* bound, TableView tv, int32_t* hidx_w, uint32_t* cbound, uint64_t* row_mass, uint64_t* norm,
+    uint32_t* rowmax, int32_t* redo, uint32_t* redo_cnt, int bit_keys, int crumb_keys, int list_keys) {
+  static_assert(D > 0 && D <= 6, "three registers of packed 16-bit sums");
+  extern __shared__ __align__(16) uint32_t lds[];  // [kNibWaves][w / 8] words: one sketch row of nibbles per wave
+  constexpr int P = (D + 1) / 2;  // registers of a key's packed buckets
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int w = (int)hp.width;
+  uint32_t* slot = lds + wv * (w >> 3);
+  for (int j = lane; j < (w >> 3); j += 64) slot[j] = 0u;
+  const int64_t nw = (int64_t)gridDim.x * kNibWaves;
+  // what bucket_q's usual route needs of the D rows, six scalar registers a
+  // row (through each_bucket<D> the whole HashParams rows stayed live, spilled,
+  // and came back with some twenty-five v_readlane per hash)
+  double qa[D], qb[D];
+  uint32_t am[D], bm[D];
+#pragma unroll
+  for (int r = 0; r < D; ++r) {
+    qa[r] = hp.qa[r];
+    qb[r] = hp.qb[r];
+    am[r] = (uint32_t)hp.ap[r] & hp.wmask;
+    bm[r] = (uint32_t)hp.bp[r];
+  }
+  // an owner's key count if this kernel builds it, else -1
+  auto owner = [&](int64_t m, int32_t hot, int32_t form, uint64_t bnd) -> int {
+    return hot < 0 && byte_class(form, m, bnd) && nib_list_row(m, w, D, false, 0, bit_keys, crumb_keys, list_keys)
+               ? (int)m
+               : -1;
+  };
+  int64_t row = (int64_t)blockIdx.x * kNibWaves + wv;
+  if (row >= nrows) return;
+  int64_t lo = lo_[row];
+  int m = owner(hi_[row] - lo, row_hot[row], tv.hidx[row], bound[row]);
+  uint64_t raw0 = lane < m ? keys.raw(lo + lane) : 0ULL;
+  for (;;) {
+    const int64_t nrow = row + nw;
+    const bool more = nrow < nrows;
+    int64_t nlo = 0, nhi = 0;
+    int32_t nhot = 0, nform = 0;
+    uint64_t nbound = 0;
+    if (more) {  // (all five loads in flight together)
+      nlo = lo_[nrow];
+      nhi = hi_[nrow];
+      nhot = row_hot[nrow];
+      nform = tv.hidx[nrow];
+      nbound = bound[nrow];
+    }
+    uint32_t pk[kKeyRegs][P];  // bucket r of key slot k: bits 16 (r & 1) of pk[k][r >> 1]
+    uint16_t* lst = nullptr;
+    if (m >= 0) {
+      lst = tv.row16(row);  // [0] = m, then [d][m] buckets
+      uint64_t raw[kKeyRegs];
+      raw[0] = raw0;
+#pragma unroll
+      for (int k = 1; k < kKeyRegs; ++k) raw[k] = lane + 64 * k < m ? keys.raw(lo + lane + 64 * k) : 0ULL;
+#pragma unroll
+      for (int k = 0; k < kKeyRegs; ++k) {
+#pragma unroll
+        for (int q = 0; q < P; ++q) pk[k][q] = 0u;
+        if (lane + 64 * k < m) {
+          uint16_t* e = lst + 1 + lane + 64 * k;
+          const uint64_t kp = keys.resolve(raw[k]);
+          const double kf = (double)(uint32_t)kp;
+          const uint32_t km = (uint32_t)kp & hp.wmask;
+          bool redo_key = (kp >> 32) != 0;
+#pragma unroll
+          for (int r = 0; r < D; ++r) {  // bucket_q without its margin branch
+            const double y = fma(qa[r], kf, qb[r]);
+            const double fl = floor(y);
+            const double fr = y - fl;
+            redo_key |= !(fr >= kQEps && fr <= 1.0 - kQEps);
+            const uint32_t q = (uint32_t)__double_as_longlong(fl + 4503599627370496.0);
+            const uint32_t c = (__umul24(am[r], km) + bm[r] + __umul24(q, 25u)) & hp.wmask;
+            e[r * m] = (uint16_t)c;
+            pk[k][r >> 1] |= c << ((r & 1) << 4);
+          }
+          if (redo_key) {  // a hash in bucket_q's margin (1 in 30,000) or a key >= 2^32: the key's rows again, by bucket()
+#pragma unroll 1
+            for (int r = 0; r < D; ++r) {
+              const uint32_t c = bucket(hp, r, kp);
+              e[r * m] = (uint16_t)c;
+#pragma unroll
+              for (int q = 0; q < P; ++q)
+                if ((r >> 1) == q)
+                  pk[k][q] = (r & 1) ? (pk[k][q] & 0xFFFFu) | (c << 16) : (pk[k][q] & 0xFFFF0000u) | c;
+            }
+          }
+        }
+      }
+    }
+    int nm = -1;
+    uint64_t nraw0 = 0ULL;
+    if (more) {
+      nm = owner(nhi - nlo, nhot, nform, nbound);
+      if (lane < nm) nraw0 = keys.raw(nlo + lane);
+    }
+    if (m >= 0) {
+      // per sketch row: the exact sum of squares (2 c + 1 per unit add,
+      // telescoping) as 16-bit fields, two rows to a register: a lane's sum is
+      // below 4 * 31, the wave's below 2^13
+      uint32_t sq[3] = {0u, 0u, 0u};
+      uint32_t vmax = 0;
+      const int ns = (m + 63) >> 6;  // live key slots (uniform): the row passes have no branch per slot
+      const bool ovf = ns == 1   ? list_rows<D, 1>(slot, pk, lane, m, sq, vmax)
+                       : ns == 2 ? list_rows<D, 2>(slot, pk, lane, m, sq, vmax)
+                       : ns == 3 ? list_rows<D, 3>(slot, pk, lane, m, sq, vmax)
+                       : ns == 4 ? list_rows<D, 4>(slot, pk, lane, m, sq, vmax)
+                                 : false;
+      if (lane == 0) lst[0] = (uint16_t)m;
+      if (ovf) {  // to k_build_bytes, which keeps the list (~row) and rewrites entries, norms and maximum
+        if (lane == 0) redo[atomicAdd(redo_cnt, 1u)] = ~(int32_t)row;
+      } else {
+#pragma unroll
+        for (int q = 0; q < P; ++q) sq[q] = wave_fold_dpp(sq[q], [](uint32_t a, uint32_t b) { return a + b; });
+        vmax = wave_fold_dpp(vmax, [](uint32_t a, uint32_t b) { return max(a, b); });  // (0 is neutral for both)
+        if (lane < D) {
+          uint32_t s = 0;
+#pragma unroll
+          for (int r = 0; r < D; ++r)
+            if (lane == r) s = (sq[r >> 1] >> ((r & 1) << 4)) & 0xFFFFu;
+          norm[row * D + lane] = s;
+        }
+        if (lane == 0) {
+          rowmax[row] = vmax;
+          row_mass[row] = (uint64_t)m;  // unit increments
+          hidx_w[row] = kFormList;
+          cbound[row] = vmax;
+        }
+      }
+    }
+    if (!more) break;
+    row = nrow;
+    lo = nlo;
+    m = nm;
+    raw0 = nraw0;
+  }
 }
 
 // The byte-class owners a counter >= 16 sent back from k_build_nibbles: the
@@ -1714,11 +1928,45 @@ int ingest_spans_device(cms_handle* h, const int64_t* d_lo, const int64_t* d_hi,
         join.armed = true;
       }
       const int64_t nib_blocks = (n + kNibWaves - 1) / kNibWaves;
-      hipLaunchKernelGGL((k_build_nibbles<kBuildStoreForm, 0>), dim3((unsigned)nib_blocks), dim3(64 * kNibWaves),
-                         (size_t)kNibWaves * (size_t)h->p.width / 2, side, d_lo, d_hi, keys, d_val, n, h->hp, row_hot,
-                         h->ws_bound.as<uint64_t>(), h->tview(), h->d_hidx, h->d_cbound, h->d_row_mass, h->d_norm,
-                         h->d_rowmax, h->d_flags, redo, redo_cnt, h->tune.bit_keys, h->tune.crumb_keys,
-                         lists_allowed(h) ? h->tune.list_keys : 0);
+      const size_t nib_lds = (size_t)kNibWaves * (size_t)h->p.width / 2;
+      // the byte class's list rows in a kernel of their own where it exists:
+      // unit increments, a power-of-two width, an unrolled depth
+#if defined(CMS_BUILD_CHEAPHASH) || defined(CMS_BUILD_GATHERHASH)  // (those replace bucket(), which it does not call)
+      const int lists_done = 0;
+#else
+      const int lists_done = !d_val && h->hp.frac_bits == 0 && h->hp.fastq && lists_allowed(h) &&
+                                     (h->p.depth == 4 || h->p.depth == 5)
+                                 ? 1
+                                 : 0;
+#endif
+      if (lists_done) {
+        auto klists = h->p.depth == 5 ? k_build_lists<kBuildStoreForm, 5> : k_build_lists<kBuildStoreForm, 4>;
+        // a grid that is resident whole (wave g takes rows g, g + G, ...):
+        // 0.87 ms alone against 0.91 ms with one owner per wave
+        if (h->lists_wgs_per_cu <= 0) {
+          int per_cu = 0;
+          CMS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, klists, 64 * kNibWaves, nib_lds));
+          h->lists_wgs_per_cu = std::max(1, per_cu);
+        }
+        const int64_t lists_blocks = std::min<int64_t>(nib_blocks, (int64_t)h->num_cus * h->lists_wgs_per_cu);
+        hipLaunchKernelGGL(klists, dim3((unsigned)lists_blocks), dim3(64 * kNibWaves), nib_lds, side, d_lo, d_hi, keys,
+                           n, h->hp, row_hot, h->ws_bound.as<uint64_t>(), h->tview(), h->d_hidx, h->d_cbound,
+                           h->d_row_mass, h->d_norm, h->d_rowmax, redo, redo_cnt, h->tune.bit_keys,
+                           h->tune.crumb_keys, h->tune.list_keys);
+      }
+      // with unit increments a byte-class owner has at most 255 keys (its
+      // bound): where every such key count makes a list row (config 3),
+      // k_build_nibbles would only read each row's spans and return (0.28 ms)
+      bool nibbles_idle = lists_done != 0;
+      for (int64_t m = 0; nibbles_idle && m < kByteKeys; ++m)
+        nibbles_idle = nib_list_row(m, h->p.width, h->p.depth, false, 0, h->tune.bit_keys, h->tune.crumb_keys,
+                                    h->tune.list_keys);
+      if (!nibbles_idle)
+        hipLaunchKernelGGL((k_build_nibbles<kBuildStoreForm, 0>), dim3((unsigned)nib_blocks), dim3(64 * kNibWaves),
+                           nib_lds, side, d_lo, d_hi, keys, d_val, n, h->hp, row_hot, h->ws_bound.as<uint64_t>(),
+                           h->tview(), h->d_hidx, h->d_cbound, h->d_row_mass, h->d_norm, h->d_rowmax, h->d_flags,
+                           redo, redo_cnt, h->tune.bit_keys, h->tune.crumb_keys,
+                           lists_allowed(h) ? h->tune.list_keys : 0, lists_done);
       // LDS: the [d][w] 4-bit image, or one sketch row of u16 counters
       const size_t mid_lds = std::max<size_t>((size_t)h->p.width * 2, (size_t)h->dw / 2);
       auto kmid = h->p.depth == 5   ? k_build_mid<kBuildStoreForm, 5, kMidThreads>

@@ -1498,12 +1498,15 @@ int top_k_all(cms_handle* h, int32_t k, int64_t* d_ids, double* d_scores, int32_
     }
     return CMS_OK;
   }
-  int rc = cosine_prepare(h);
+  // (a width that is no multiple of the K slice has no limb images: the
+  // per-row path's exact pair kernel, as top_k_rows decides for itself)
+  const bool mfma = mfma_eligible(h);
+  int rc = mfma ? cosine_prepare(h) : CMS_OK;
   if (rc) return rc;
   const int64_t n = h->n;
   const BigCfg cfg = big_config(h);
   const int64_t nm = h->n_hot_limb, ns = n - nm;
-  if (!cfg.nstage || (nm > 0 && !h->vl_ok) || h->n_inexact_rows != 0 || k > kCandCap / 2) {
+  if (!mfma || !cfg.nstage || (nm > 0 && !h->vl_ok) || h->n_inexact_rows != 0 || k > kCandCap / 2) {
     if (nshards == 1) return top_k_rows(h, 0, n, k, d_ids, d_scores, d_counts);  // per-row slab path
     // per-row slab path for this shard's rows only; the other rows stay empty
     CMS_HIP(hipMemsetAsync(d_counts, 0, sizeof(int32_t) * n, h->stream));

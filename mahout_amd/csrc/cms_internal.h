@@ -237,6 +237,7 @@ struct cms_handle {
   int device = 0;
   int num_cus = 256;  // compute units of the device (persistent grids)
   int stream_wgs_per_cu = 0;  // resident workgroups per CU of the streamed mid build (occupancy query, once)
+  int lists_wgs_per_cu = 0;   // ... of the byte-class list build (k_build_lists)
   hipStream_t stream = nullptr;
   // side stream of the row build: the byte-class kernels run beside the slot
   // rows (ordered by ev_fork2 / ev_join2 on the handle's stream), and the

@@ -1,8 +1,8 @@
 """Per-step phase durations of the headline ingest from a rocprofv3 kernel
 trace (scripts/profile_r03.sh ingest): for every step, the build scope
 (first build-kernel start -> last build-kernel end: k_build_rows on the
-handle's stream, k_build_nibbles / k_build_mid / k_build_bytes on the side
-stream, which overlap) and the partition (k_hot_sample start -> k_p2_scatter
+handle's stream, k_build_nibbles / k_build_lists / k_build_mid / k_build_bytes
+on the side streams, which overlap) and the partition (k_hot_sample start -> k_p2_scatter
 end), so the bench's build roofline (algorithmic bytes / scope time) can be
 recomputed from the committed trace.
 
@@ -11,7 +11,7 @@ import csv
 import statistics
 import sys
 
-BUILD = ("k_build_rows", "k_build_nibbles", "k_build_mid", "k_build_bytes")
+BUILD = ("k_build_rows", "k_build_nibbles", "k_build_lists", "k_build_mid", "k_build_bytes")
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
 steps, part = [], []
 cur_b, cur_p = None, None
