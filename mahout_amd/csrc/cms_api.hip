@@ -398,6 +398,7 @@ static int create_impl(const cms_params* p, bool per_owner, cms_handle** out) {
       (e = hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking)) != hipSuccess ||
       (e = hipStreamCreateWithFlags(&h->side_stream2, hipStreamNonBlocking)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&h->ev_join3, hipEventDisableTiming)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&h->ev_mid_lists, hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&h->ev_spans, hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&h->ev_plan, hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&h->ev_fork2, hipEventDisableTiming)) != hipSuccess ||
@@ -459,6 +460,7 @@ void cms_destroy(cms_handle* h) {
   if (h->side_stream) (void)hipStreamSynchronize(h->side_stream);
   if (h->side_stream2) (void)hipStreamSynchronize(h->side_stream2);
   if (h->ev_join3) (void)hipEventDestroy(h->ev_join3);
+  if (h->ev_mid_lists) (void)hipEventDestroy(h->ev_mid_lists);
   if (h->ev_spans) (void)hipEventDestroy(h->ev_spans);
   if (h->ev_plan) (void)hipEventDestroy(h->ev_plan);
   if (h->ev_fork2) (void)hipEventDestroy(h->ev_fork2);

@@ -523,46 +523,82 @@ __global__ __launch_bounds__(kBuildThreads) __attribute__((amdgpu_waves_per_eu(k
 // A mid list is TWO-ENDED: cnt[0] owners from the front of its cap entries,
 // cnt[1] more from the back.  The streamed list holds the long owners in
 // front and the others behind; the cached list holds the cached owners behind
-// and takes in front the streamed owners that the one-pass kernel sends back.
+// and takes in front the streamed owners that the one-pass kernel sends back
+// (and the list rows that k_build_mid_lists sends back).  The cached owners
+// that k_build_mid_lists builds (mid_list_row, where that kernel exists) have
+// a one-ended list of their own.
 constexpr int kMidThreads = 256;  // threads per owner (a workgroup) of the row-at-a-time mid build
 constexpr int64_t kMidCachedKeys = (int64_t)kMidThreads * kKeyRegs;
 constexpr int64_t kStreamBigKeys = 4096;
 __device__ __forceinline__ int32_t list2_at(const int32_t* list, uint32_t cap, uint32_t nfront, uint32_t i) {
   return i < nfront ? list[i] : list[cap - 1u - (i - nfront)];
 }
+// A byte-class owner's first form: 1-bit rows up to bit_keys keys
+// (Tunables::bit_keys, 64), 2-bit up to crumb_keys (256), else 4-bit
+__host__ __device__ __forceinline__ int nib_first_bits(int64_t m, int w, int bit_keys, int crumb_keys) {
+  return (m <= bit_keys && (w & 127) == 0) ? 1 : (m <= crumb_keys && (w & 63) == 0) ? 2 : 4;
+}
+// ... stored as a list row: unit increments, at most list_keys keys, and the
+// list (2 + 2 d m bytes) no larger than the dense row it would take first
+__host__ __device__ __forceinline__ bool nib_list_row(int64_t m, int w, int d, bool weighted, int frac_bits,
+                                                      int bit_keys, int crumb_keys, int list_keys) {
+  return m <= list_keys && !weighted && frac_bits == 0 &&
+         2 + 2 * (int64_t)d * m <= ((int64_t)d * w * nib_first_bits(m, w, bit_keys, crumb_keys)) / 8;
+}
+// A cached mid owner stored as a list row (while no counter passes 255): unit
+// increments, at most list_keys keys (kMidListKeys, or 0 without lists), d m
+// entries within the list's 8192, and the list smaller than even the 4-bit
+// row.  mid_rows, k_build_classes and k_build_mid_lists decide by this.
+__host__ __device__ __forceinline__ bool mid_list_row(int64_t m, int w, int d, bool weighted, int frac_bits,
+                                                      int list_keys) {
+  return m <= list_keys && !weighted && frac_bits == 0 && (int64_t)d * m <= 8192 &&
+         2 + 2 * (int64_t)d * m < (int64_t)d * w / 2;
+}
 // counters of the class lists (one zeroed block per build)
-enum { kCntSlot = 0, kCntMid = 1 /* front, back */, kCntStream = 3 /* front, back */, kCntTicket = 5, kCntWords = 8 };
+enum {
+  kCntSlot = 0,
+  kCntMid = 1 /* front, back */,
+  kCntStream = 3 /* front, back */,
+  kCntTicket = 5,
+  kCntMidLists = 6,
+  kCntWords = 8
+};
 constexpr int kClassChunk = 4096;
+// mid_lists_keys: kMidListKeys where k_build_mid_lists runs in this build (its
+// owners then leave the cached list for mid_lists), else 0
 __global__ __launch_bounds__(256) void k_build_classes(const int64_t* lo_, const int64_t* hi_, int64_t nrows,
                                                        const int32_t* hidx, const uint64_t* bound, int32_t* slot_list,
-                                                       int32_t* mid_list, int32_t* stream_list, uint32_t* cnt) {
-  // both two-ended, as the lists they feed (an owner is in one class): slot
+                                                       int32_t* mid_list, int32_t* stream_list, uint32_t* cnt,
+                                                       int32_t* mid_lists, int mid_lists_keys, int d, int w) {
+  // two-ended, as the lists they feed (an owner is in one class): slot
   // rows from the front of s_own and cached owners from its back, long
   // streamed owners from the front of s_str and short ones from its back
-  __shared__ int32_t s_own[kClassChunk], s_str[kClassChunk];
-  __shared__ uint32_t s_n[4], s_b[4];  // slot, cached, streamed long, streamed short
+  __shared__ int32_t s_own[kClassChunk], s_str[kClassChunk], s_lst[kClassChunk];
+  __shared__ uint32_t s_n[5], s_b[5];  // slot, cached, streamed long, streamed short, cached list rows
   const int lane = (int)__lane_id();
   const int tid = threadIdx.x;
   const uint32_t cap = (uint32_t)nrows;
   const unsigned long long below = (1ULL << lane) - 1ULL;
   for (int64_t r0 = (int64_t)blockIdx.x * kClassChunk; r0 < nrows; r0 += (int64_t)gridDim.x * kClassChunk) {
-    if (tid < 4) s_n[tid] = 0;
+    if (tid < 5) s_n[tid] = 0;
     __syncthreads();
     for (int64_t r = r0 + tid; r < r0 + kClassChunk; r += 256) {  // (whole waves: the ballots)
-      bool is[4] = {false, false, false, false};
+      bool is[5] = {false, false, false, false, false};
       if (r < nrows) {
         const int32_t sl = hidx[r];
         const int64_t m = hi_[r] - lo_[r];
         is[0] = sl >= 0;
         const bool is_mid = !is[0] && !byte_class(sl, m, bound[r]);
-        is[1] = is_mid && m <= kMidCachedKeys;
+        const bool cached = is_mid && m <= kMidCachedKeys;
+        is[4] = cached && mid_list_row(m, w, d, false, 0, mid_lists_keys);
+        is[1] = cached && !is[4];
         is[2] = is_mid && m > kStreamBigKeys;
-        is[3] = is_mid && !is[1] && !is[2];
+        is[3] = is_mid && !cached && !is[2];
       }
-      unsigned long long mk[4];
-      uint32_t b[4] = {0, 0, 0, 0};
+      unsigned long long mk[5];
+      uint32_t b[5] = {0, 0, 0, 0, 0};
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
+      for (int k = 0; k < 5; ++k) {
         mk[k] = __ballot(is[k]);
         if (lane == 0 && mk[k]) b[k] = atomicAdd(&s_n[k], (uint32_t)__popcll(mk[k]));
         b[k] = (uint32_t)__shfl((int)b[k], 0, 64) + (uint32_t)__popcll(mk[k] & below);
@@ -571,10 +607,11 @@ __global__ __launch_bounds__(256) void k_build_classes(const int64_t* lo_, const
       if (is[1]) s_own[kClassChunk - 1 - b[1]] = (int32_t)r;
       if (is[2]) s_str[b[2]] = (int32_t)r;
       if (is[3]) s_str[kClassChunk - 1 - b[3]] = (int32_t)r;
+      if (is[4]) s_lst[b[4]] = (int32_t)r;
     }
     __syncthreads();
-    if (tid < 4) {
-      const int ci = tid == 0 ? kCntSlot : tid == 1 ? kCntMid + 1 : kCntStream + tid - 2;
+    if (tid < 5) {
+      const int ci = tid == 0 ? kCntSlot : tid == 1 ? kCntMid + 1 : tid == 4 ? kCntMidLists : kCntStream + tid - 2;
       s_b[tid] = s_n[tid] ? atomicAdd(&cnt[ci], s_n[tid]) : 0u;
     }
     __syncthreads();
@@ -582,6 +619,7 @@ __global__ __launch_bounds__(256) void k_build_classes(const int64_t* lo_, const
     for (uint32_t i = tid; i < s_n[1]; i += 256) mid_list[cap - 1u - (s_b[1] + i)] = s_own[kClassChunk - 1 - i];
     for (uint32_t i = tid; i < s_n[2]; i += 256) stream_list[s_b[2] + i] = s_str[i];
     for (uint32_t i = tid; i < s_n[3]; i += 256) stream_list[cap - 1u - (s_b[3] + i)] = s_str[kClassChunk - 1 - i];
+    for (uint32_t i = tid; i < s_n[4]; i += 256) mid_lists[s_b[4] + i] = s_lst[i];
     __syncthreads();
   }
 }
@@ -652,14 +690,15 @@ __device__ __forceinline__ void mid_rows(
     // keys' buckets leave instead of the image (u16 counters -- a count past
     // 255 -- keep the dense row)
     const int64_t m = hi - lo;
-    const bool as_list = cached && m <= list_keys && vals == nullptr && hp.frac_bits == 0 &&
-                         (int64_t)hp.depth * m <= 8192 && 2 + 2 * (int64_t)hp.depth * m < (int64_t)hp.depth * w / 2;
+    const bool as_list = cached && mid_list_row(m, w, hp.depth, vals != nullptr, hp.frac_bits, list_keys);
     uint16_t* lst = tv.row16(row);
     int level = -1;  // the form that holds the owner: 0 4-bit, 1 u8, 2 u16 (the class bound keeps every counter < 2^16)
     uint32_t vmax = 0;
     // the first form tried (Tunables::mid_u4_keys / mid_u8_keys); a list row
     // leaves its entries in the 4-bit pass, so it always takes that pass
-    const int start = as_list || m <= u4_keys ? 0 : m <= u8_keys ? 1 : 2;
+    // ... unless k_build_mid_lists sent it back (the cached owners in front
+    // of the list): a counter passed 255, so the u16 rows at once
+    const int start = cached && li < nfront ? 2 : as_list || m <= u4_keys ? 0 : m <= u8_keys ? 1 : 2;
     bool mass_pending = !cached;  // uncached keys: the mass is summed by the first pass over them
     // ALL sketch rows in one key pass in a [d][w] 4-bit image.  (A [d][w] u8
     // image after a 4-bit overflow -- a Zipf key set repeats its popular keys,
@@ -1070,19 +1109,7 @@ __global__ __launch_bounds__(MT) __attribute__((amdgpu_waves_per_eu(MT == kStrea
 constexpr int kMidGridPerCu = 8;  // persistent k_build_mid workgroups per CU
 constexpr int kNibWaves = 4;
 // owners with at most Tunables::bit_keys (64) keys try 1-bit rows first, with
-// at most crumb_keys (256) 2-bit rows
-// A byte-class owner's first form: 1-bit rows up to bit_keys keys, 2-bit up
-// to crumb_keys, else 4-bit
-__host__ __device__ __forceinline__ int nib_first_bits(int64_t m, int w, int bit_keys, int crumb_keys) {
-  return (m <= bit_keys && (w & 127) == 0) ? 1 : (m <= crumb_keys && (w & 63) == 0) ? 2 : 4;
-}
-// ... stored as a list row: unit increments, at most list_keys keys, and the
-// list (2 + 2 d m bytes) no larger than the dense row it would take first
-__host__ __device__ __forceinline__ bool nib_list_row(int64_t m, int w, int d, bool weighted, int frac_bits,
-                                                      int bit_keys, int crumb_keys, int list_keys) {
-  return m <= list_keys && !weighted && frac_bits == 0 &&
-         2 + 2 * (int64_t)d * m <= ((int64_t)d * w * nib_first_bits(m, w, bit_keys, crumb_keys)) / 8;
-}
+// at most crumb_keys (256) 2-bit rows (nib_first_bits; nib_list_row: the list rows)
 
 // Compact layout of a fresh build (row_layout): each row's arena capacity in
 // 128-B units, by what its class's kernel can store -- a hot row nothing (its
@@ -1439,6 +1466,226 @@ __global__ __launch_bounds__(64 * kNibWaves) __attribute__((amdgpu_waves_per_eu(
     lo = nlo;
     m = nm;
     raw0 = nraw0;
+  }
+}
+
+// The cached mid owners that mid_list_row makes list rows (256 to 1024 keys
+// at config 3), under k_build_lists' conditions -- unit increments, a
+// power-of-two width (hp.fastq), depth D -- and in its shape: ONE WAVE per
+// owner, no barrier and no pass over w.  The result needs the keys' buckets
+// in key order, each sketch row's sum of squares and the largest counter.
+// Each key is hashed once for all D rows (the six hash scalars a row and the
+// redo_key route of k_build_lists), its entries stored as they are produced
+// and kept packed two to a register, up to kMidListSlots key slots a lane.
+// The wave's LDS slot holds one sketch row of w u8 counters: per sketch row
+// every add of the owner is issued before an old counter is read (a lane past
+// the last key adds 0 to a word of its own), 2 old + 1 per add telescopes to the sum of
+// squares (32 bits a row: a lane's sixteen adds reach 16 * 511), and zero is
+// stored to just the words added into once the row's adds are all issued.  A
+// counter that would pass 255 carries inside a word the row clears anyway;
+// the owner then leaves its rows (wave-uniform) for the front of the cached
+// list, where mid_rows builds its u16 rows -- the form mid_rows alone gives
+// it.  The grid is resident and wave g takes list entries g, g + G, ...: the
+// entry is read two owners ahead, the next owner's spans and place before the
+// hashes, its first key slot before the row passes.  SV is unused.
+constexpr int kMidListWaves = 4;       // waves per workgroup, each with a slot of its own
+constexpr int kMidListSlots = 16;      // key slots per lane: kMidListKeys keys in registers
+constexpr int kMidListGroup = 4;       // key slots whose loads are in flight together; the row passes go by whole groups
+constexpr int kMidListSlotMax = 8192;  // widest sketch row it takes: 32 KB of LDS per workgroup, four workgroups per CU
+static_assert(64 * kMidListSlots == kMidListKeys && kMidListSlots % kMidListGroup == 0, "every cached list row fits");
+
+// Its row passes for an owner of ns live key slots (uniform: a scalar branch
+// per slot, none per lane).  Bit k of `live`: the lane's key slot k holds a key.
+template <int D>
+__device__ __forceinline__ bool mid_list_rows(uint32_t* slot, const uint32_t (&pk)[kMidListSlots][(D + 1) / 2],
+                                              uint32_t live, int ns, uint32_t (&sq)[D], uint32_t& vmax) {
+  bool ovf = false;
+#pragma unroll
+  for (int r = 0; r < D; ++r) {
+    uint32_t old[kMidListSlots];
+#pragma unroll
+    for (int k = 0; k < kMidListSlots; ++k)
+      if (k < ns) {
+        const uint32_t c = (pk[k][r >> 1] >> ((r & 1) << 4)) & 0xFFFFu;
+        old[k] = atomicAdd(&slot[c >> 2], ((live >> k) & 1u) << ((c & 3u) << 3));
+      }
+#pragma unroll
+    for (int k = 0; k < kMidListSlots; ++k)
+      if (k < ns) {
+        // (the bucket unpacked again: kept from the adds, the sixteen addresses
+        // and shifts spilled beside the packed buckets and the old counters)
+        uint32_t p = pk[k][r >> 1];
+        asm volatile("" : "+v"(p));
+        const uint32_t c = (p >> ((r & 1) << 4)) & 0xFFFFu;
+        const uint32_t lv = (live >> k) & 1u;
+        const uint32_t o = (old[k] >> ((c & 3u) << 3)) & 255u;
+        const uint32_t nv = (o + 1u) * lv;
+        ovf |= nv > 255u;  // the add carried into the next counter (or out of the word)
+        sq[r] += (2u * o + 1u) * lv;
+        vmax = max(vmax, nv);
+        // zero to just the words added into, after every lane's add of this
+        // row (one wave's LDS operations execute in order): 388 us alone
+        // against 399 us with the slot zeroed whole before every row
+        slot[c >> 2] = 0u;
+      }
+    if (__ballot(ovf)) return true;
+  }
+  return false;
+}
+
+template <int SV, int D>
+__global__ __launch_bounds__(64 * kMidListWaves) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_build_mid_lists(
+    const int64_t* lo_, const int64_t* hi_, Keys keys, HashParams hp, const int32_t* list, const uint32_t* list_cnt,
+    TableView tv, int32_t* hidx_w, uint32_t* cbound, uint64_t* row_mass, uint64_t* norm, uint32_t* rowmax,
+    int32_t* redo, uint32_t* redo_cnt) {
+  extern __shared__ __align__(16) uint32_t lds[];  // [kMidListWaves][w / 4] words: one sketch row of u8 counters per wave
+  constexpr int P = (D + 1) / 2;  // registers of a key's packed buckets
+  constexpr int NSL = kMidListSlots, GS = kMidListGroup, NGR = NSL / GS;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int w = (int)hp.width;
+  uint32_t* slot = lds + wv * (w >> 2);
+  for (int j = lane; j < (w >> 2); j += 64) slot[j] = 0u;
+  const uint32_t count = list_cnt[0];
+  // a lane past the owner's last key adds 0 to a word of its own (the lanes of
+  // one wave adding to one word would take their turns)
+  const uint32_t idle = ((4u * (uint32_t)lane) & hp.wmask) * 0x10001u;
+  double qa[D], qb[D];  // (k_build_lists: what bucket_q's usual route needs, six scalar registers a row)
+  uint32_t am[D], bm[D];
+#pragma unroll
+  for (int r = 0; r < D; ++r) {
+    qa[r] = hp.qa[r];
+    qb[r] = hp.qb[r];
+    am[r] = (uint32_t)hp.ap[r] & hp.wmask;
+    bm[r] = (uint32_t)hp.bp[r];
+  }
+  // a fixed stride over the list: 388 us alone against 1227 us with every
+  // wave drawing its entries from one ticket counter (a wave's owner is a few
+  // microseconds of work; the owners' key counts span only 4x)
+  const uint32_t stride = gridDim.x * kMidListWaves;  // (count + 2 stride < 2^32)
+  const uint32_t li = blockIdx.x * kMidListWaves + wv;
+  if (li >= count) return;
+  int32_t row = list[li];
+  int32_t row1 = li + stride < count ? list[li + stride] : -1;
+  uint32_t li2 = li + 2u * stride;
+  int64_t lo = lo_[row];
+  int m = (int)(hi_[row] - lo);
+  int64_t base = tv.base(row);
+  uint64_t raw0 = lane < m ? keys.raw(lo + lane) : 0ULL;
+  for (;;) {
+    const int32_t row2 = li2 < count ? list[li2] : -1;
+    li2 += stride;
+    int64_t nlo = 0, nhi = 0, nbase = 0;
+    if (row1 >= 0) {  // (the three loads in flight together)
+      nlo = lo_[row1];
+      nhi = hi_[row1];
+      nbase = tv.base(row1);
+    }
+    uint16_t* lst = tv.t16 + base;  // [0] = m, then [d][m] buckets
+    uint32_t pk[NSL][P];            // bucket r of key slot k: bits 16 (r & 1) of pk[k][r >> 1]
+    {
+      uint64_t cur[GS], nxt[GS];
+      cur[0] = raw0;
+#pragma unroll
+      for (int j = 1; j < GS; ++j) cur[j] = lane + 64 * j < m ? keys.raw(lo + lane + 64 * j) : 0ULL;
+#pragma unroll
+      for (int g = 0; g < NGR; ++g) {
+#pragma unroll
+        for (int j = 0; j < GS; ++j) nxt[j] = 0ULL;
+        if (g + 1 < NGR && 64 * GS * (g + 1) < m) {  // (uniform) the next group's keys before this group's hashes
+#pragma unroll
+          for (int j = 0; j < GS; ++j) {
+            const int t = lane + 64 * (GS * (g + 1) + j);
+            if (t < m) nxt[j] = keys.raw(lo + t);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < GS; ++j)
+#pragma unroll
+          for (int q = 0; q < P; ++q) pk[GS * g + j][q] = idle;
+        if (64 * GS * g < m) {  // (uniform)
+#pragma unroll
+          for (int j = 0; j < GS; ++j) {
+            const int k = GS * g + j;
+            if (lane + 64 * k < m) {
+              uint16_t* e = lst + 1 + lane + 64 * k;
+              const uint64_t kp = keys.resolve(cur[j]);
+              const double kf = (double)(uint32_t)kp;
+              const uint32_t km = (uint32_t)kp & hp.wmask;
+              bool redo_key = (kp >> 32) != 0;
+#pragma unroll
+              for (int q = 0; q < P; ++q) pk[k][q] = 0u;
+#pragma unroll
+              for (int r = 0; r < D; ++r) {  // bucket_q without its margin branch
+                const double y = fma(qa[r], kf, qb[r]);
+                const double fl = floor(y);
+                const double fr = y - fl;
+                redo_key |= !(fr >= kQEps && fr <= 1.0 - kQEps);
+                const uint32_t q = (uint32_t)__double_as_longlong(fl + 4503599627370496.0);
+                const uint32_t c = (__umul24(am[r], km) + bm[r] + __umul24(q, 25u)) & hp.wmask;
+                e[r * m] = (uint16_t)c;
+                pk[k][r >> 1] |= c << ((r & 1) << 4);
+              }
+              if (redo_key) {  // a hash in bucket_q's margin or a key >= 2^32: the key's rows again, by bucket()
+#pragma unroll 1
+                for (int r = 0; r < D; ++r) {
+                  const uint32_t c = bucket(hp, r, kp);
+                  e[r * m] = (uint16_t)c;
+#pragma unroll
+                  for (int q = 0; q < P; ++q)
+                    if ((r >> 1) == q)
+                      pk[k][q] = (r & 1) ? (pk[k][q] & 0xFFFFu) | (c << 16) : (pk[k][q] & 0xFFFF0000u) | c;
+                }
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < GS; ++j) cur[j] = nxt[j];
+      }
+    }
+    int nm = 0;
+    uint64_t nraw0 = 0ULL;
+    if (row1 >= 0) {
+      nm = (int)(nhi - nlo);
+      if (lane < nm) nraw0 = keys.raw(nlo + lane);
+    }
+    uint32_t sq[D];
+#pragma unroll
+    for (int r = 0; r < D; ++r) sq[r] = 0u;
+    uint32_t vmax = 0;
+    const int nf = min(max((m - lane + 63) >> 6, 0), NSL);  // the lane's key slots
+    const uint32_t live = (1u << nf) - 1u;
+    const int ns = (m + 63) >> 6;  // live key slots (uniform)
+    const bool ovf = mid_list_rows<D>(slot, pk, live, ns, sq, vmax);
+    if (ovf) {  // to mid_rows, which rewrites the whole slot as u16 rows
+      if (lane == 0) redo[atomicAdd(redo_cnt, 1u)] = row;
+    } else {
+#pragma unroll
+      for (int r = 0; r < D; ++r) sq[r] = wave_fold_dpp(sq[r], [](uint32_t a, uint32_t b) { return a + b; });
+      vmax = wave_fold_dpp(vmax, [](uint32_t a, uint32_t b) { return max(a, b); });  // (0 is neutral for both)
+      if (lane < D) {
+        uint32_t s = 0;
+#pragma unroll
+        for (int r = 0; r < D; ++r)
+          if (lane == r) s = sq[r];
+        norm[(int64_t)row * D + lane] = s;
+      }
+      if (lane == 0) {
+        lst[0] = (uint16_t)m;
+        rowmax[row] = vmax;
+        row_mass[row] = (uint64_t)m;  // unit increments
+        hidx_w[row] = kFormList;
+        cbound[row] = vmax;
+      }
+    }
+    if (row1 < 0) break;
+    row = row1;
+    lo = nlo;
+    m = nm;
+    base = nbase;
+    raw0 = nraw0;
+    row1 = row2;
   }
 }
 
@@ -1885,20 +2132,35 @@ int ingest_spans_device(cms_handle* h, const int64_t* d_lo, const int64_t* d_hi,
       // the ones a counter >= 16 sends back) and mid rows -> k_build_mid on the
       // side stream, so the classes' kernels overlap (their tails no longer
       // leave CUs idle)
-      CMS_HIP(h->ws_blist.ensure(sizeof(int32_t) * (size_t)(3 * n + kCntWords)));
+      CMS_HIP(h->ws_blist.ensure(sizeof(int32_t) * (size_t)(4 * n + kCntWords)));
       int32_t* slot_list = h->ws_blist.as<int32_t>();
-      int32_t* mid_list = slot_list + n;     // two-ended: sent-back streamed owners, cached owners
+      int32_t* mid_list = slot_list + n;     // two-ended: sent-back streamed owners and list rows, cached owners
       int32_t* stream_list = mid_list + n;   // two-ended: owners above kStreamBigKeys keys, the others
-      uint32_t* lcnt = reinterpret_cast<uint32_t*>(stream_list + n);  // kCnt*
+      int32_t* mid_lists = stream_list + n;  // the cached owners of k_build_mid_lists
+      uint32_t* lcnt = reinterpret_cast<uint32_t*>(mid_lists + n);  // kCnt*
       CMS_HIP(h->ws_plist.ensure(sizeof(int32_t) * (size_t)(n + 1)));
       int32_t* redo = h->ws_plist.as<int32_t>();
       uint32_t* redo_cnt = reinterpret_cast<uint32_t*>(redo + n);
+      // the byte class's list rows in a kernel of their own where it exists:
+      // unit increments, a power-of-two width, an unrolled depth
+#if defined(CMS_BUILD_CHEAPHASH) || defined(CMS_BUILD_GATHERHASH)  // (those replace bucket(), which it does not call)
+      const int lists_done = 0;
+#else
+      const int lists_done = !d_val && h->hp.frac_bits == 0 && h->hp.fastq && lists_allowed(h) &&
+                                     (h->p.depth == 4 || h->p.depth == 5)
+                                 ? 1
+                                 : 0;
+#endif
+      // ... and the cached mid owners' (k_build_mid_lists), while a wave's
+      // slot of w u8 counters leaves LDS for four waves per SIMD
+      const bool mid_lists_done = lists_done && h->p.width <= kMidListSlotMax;
       CMS_HIP(hipMemsetAsync(lcnt, 0, kCntWords * sizeof(uint32_t), h->stream));
       CMS_HIP(hipMemsetAsync(redo_cnt, 0, sizeof(uint32_t), h->stream));
       hipLaunchKernelGGL(k_build_classes,
                          dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kClassChunk - 1) / kClassChunk, 1024))),
                          dim3(256), 0, h->stream, d_lo, d_hi, n, h->d_hidx, h->ws_bound.as<uint64_t>(), slot_list,
-                         mid_list, stream_list, lcnt);
+                         mid_list, stream_list, lcnt, mid_lists, mid_lists_done ? kMidListKeys : 0, h->p.depth,
+                         h->p.width);
       CMS_HIP(hipGetLastError());
       if (h->plan_side_active) return set_error(CMS_E_STATE, "internal: side stream used while swapped for the plan");
       hipStream_t side = h->side_stream ? h->side_stream : h->stream;
@@ -1929,16 +2191,25 @@ int ingest_spans_device(cms_handle* h, const int64_t* d_lo, const int64_t* d_hi,
       }
       const int64_t nib_blocks = (n + kNibWaves - 1) / kNibWaves;
       const size_t nib_lds = (size_t)kNibWaves * (size_t)h->p.width / 2;
-      // the byte class's list rows in a kernel of their own where it exists:
-      // unit increments, a power-of-two width, an unrolled depth
-#if defined(CMS_BUILD_CHEAPHASH) || defined(CMS_BUILD_GATHERHASH)  // (those replace bucket(), which it does not call)
-      const int lists_done = 0;
-#else
-      const int lists_done = !d_val && h->hp.frac_bits == 0 && h->hp.fastq && lists_allowed(h) &&
-                                     (h->p.depth == 4 || h->p.depth == 5)
-                                 ? 1
-                                 : 0;
-#endif
+      // the cached mid owners' list rows first on the byte class's stream: the
+      // cached k_build_mid on the other side stream waits for them, since it
+      // builds the owners they send back
+      if (mid_lists_done) {
+        auto kml = h->p.depth == 5 ? k_build_mid_lists<kBuildStoreForm, 5> : k_build_mid_lists<kBuildStoreForm, 4>;
+        const size_t ml_lds = (size_t)kMidListWaves * (size_t)h->p.width;
+        if (h->mid_lists_wgs_per_cu <= 0) {  // a grid that is resident whole (wave g takes list entries g, g + G, ...)
+          int per_cu = 0;
+          CMS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kml, 64 * kMidListWaves, ml_lds));
+          h->mid_lists_wgs_per_cu = std::max(1, per_cu);
+        }
+        const int64_t ml_blocks = std::min<int64_t>((n + kMidListWaves - 1) / kMidListWaves,
+                                                    (int64_t)h->num_cus * h->mid_lists_wgs_per_cu);
+        hipLaunchKernelGGL(kml, dim3((unsigned)ml_blocks), dim3(64 * kMidListWaves), ml_lds, side, d_lo, d_hi, keys,
+                           h->hp, (const int32_t*)mid_lists, (const uint32_t*)(lcnt + kCntMidLists), h->tview(),
+                           h->d_hidx, h->d_cbound, h->d_row_mass, h->d_norm, h->d_rowmax, mid_list, lcnt + kCntMid);
+        CMS_HIP(hipGetLastError());
+        if (side2 != side) CMS_HIP(hipEventRecord(h->ev_mid_lists, side));
+      }
       if (lists_done) {
         auto klists = h->p.depth == 5 ? k_build_lists<kBuildStoreForm, 5> : k_build_lists<kBuildStoreForm, 4>;
         // a grid that is resident whole (wave g takes rows g, g + G, ...):
@@ -2001,6 +2272,7 @@ int ingest_spans_device(cms_handle* h, const int64_t* d_lo, const int64_t* d_hi,
       } else {
         launch_mid(kmid, kMidThreads, mid_grid, mid_lds, stream_list, lcnt + kCntStream);
       }
+      if (mid_lists_done && side2 != side) CMS_HIP(hipStreamWaitEvent(side2, h->ev_mid_lists, 0));
       launch_mid(kmid, kMidThreads, mid_grid, mid_lds, mid_list, lcnt + kCntMid);
       hipLaunchKernelGGL(k_build_bytes<kBuildStoreForm>, dim3((unsigned)std::min<int64_t>(n, (int64_t)h->num_cus * 2)),
                          dim3(kBuildThreads), (size_t)h->dw, side, d_lo, d_hi, keys, d_val, h->hp, redo, redo_cnt,

@@ -238,6 +238,7 @@ struct cms_handle {
   int num_cus = 256;  // compute units of the device (persistent grids)
   int stream_wgs_per_cu = 0;  // resident workgroups per CU of the streamed mid build (occupancy query, once)
   int lists_wgs_per_cu = 0;   // ... of the byte-class list build (k_build_lists)
+  int mid_lists_wgs_per_cu = 0;  // ... of the cached mid owners' list build (k_build_mid_lists)
   hipStream_t stream = nullptr;
   // side stream of the row build: the byte-class kernels run beside the slot
   // rows (ordered by ev_fork2 / ev_join2 on the handle's stream), and the
@@ -246,6 +247,7 @@ struct cms_handle {
   hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr;  // byte / mid class kernels beside the slot rows
   hipStream_t side_stream2 = nullptr;                 // the mid class beside the byte class (Tunables::build_streams 3)
   hipEvent_t ev_join3 = nullptr;
+  hipEvent_t ev_mid_lists = nullptr;  // k_build_mid_lists (byte class's stream) done: the cached k_build_mid takes its send-backs
   // the owner spans of a partition are ready (recorded before its last
   // scatter): the build plan may start on the side stream meanwhile
   hipEvent_t ev_spans = nullptr, ev_plan = nullptr;
@@ -287,7 +289,7 @@ struct cms_handle {
   bool forms_ok = false;            // dw % 32 == 0: fresh builds may store u8 / nibble forms
   cms::DevBuf hot_tab;              // [hot_cap][d][w] u32 counters of the hot rows
   cms::DevBuf ws_bound, ws_force, ws_plist;  // promotion scratch: u64 [n], u8 [n], i32 [n] + count
-  cms::DevBuf ws_blist;                      // row build: slot-row, cached-mid and streamed-mid row lists + counts
+  cms::DevBuf ws_blist;                      // row build: slot-row, cached-mid, streamed-mid and mid-list row lists + counts
   cms::DevBuf ws_layout;                     // row layout: capacities / scan (u32 [2n + ...]); widen: movers
   int64_t hot_cap = 0, hot_used = 0;
   cms::TableView tview() const {
