@@ -445,6 +445,55 @@ int cms_get_owner_shapes(cms_handle* h, double* delta, double* epsilon, int32_t*
  * fp64 [depth][width] (capacity in doubles; out NULL returns the shape only). */
 int cms_read_owner_sketch(cms_handle* h, int64_t id, double* out, int64_t capacity, int32_t* width, int32_t* depth);
 
+/* ---- checkpoint and restore of the sketch table ------------------------------
+ * The reference has no counterpart: CosineCM rebuilds every sketch from the
+ * DataModel (its own persistence is the CountMinSketchConfig's delta/epsilon
+ * cache).  A checkpoint image carries every owner row in the form the table
+ * stores it in (list / 1 / 2 / 4 / 8 / 16-bit rows, u32 hot rows, fp64), so it
+ * is about cms_stats.stored_bytes long; the format (version 1, little-endian)
+ * is documented byte for byte in DESIGN.md 3 "Checkpoint image" and read
+ * without the library by mahout_amd/checkpoint.py.  A file is the image; a
+ * device image is the same bytes.
+ *
+ * Saving: fixed-shape handles (CMS_E_STATE on a per-owner handle), before or
+ * after cms_finalize; on a multi-rank handle only once merged and with no COO
+ * batch ingested since the last cms_finalize (every rank then holds the whole
+ * table; CMS_E_STATE otherwise).  The call synchronises and
+ * reports a pending device-ingest error as cms_synchronize would; it writes
+ * only on CMS_OK.
+ *
+ * Loading: the handle must be empty (new, or after cms_reset), fixed-shape and
+ * without a communicator (CMS_E_STATE otherwise), and its depth, width,
+ * num_owners, counter type and frac_bits must equal the image's (CMS_E_PARAM).
+ * The image's hash parameters and owner IDs are installed as
+ * cms_set_hash_params / cms_set_owner_ids would, pairs_ingested is restored,
+ * and the handle is left "ingested, not finalized": cms_finalize derives the
+ * norms (the image stores none), later ingests behave as on the saving handle.
+ * Header, directory and section bounds are checked on the host before the
+ * device sees anything, the payload checksum and every list row's entries on
+ * the device while copying; on any failure the call returns CMS_E_PARAM and
+ * the handle is empty and usable, as after cms_reset.  The restored rows are
+ * laid out anew (no holes where rows moved), in whatever layout the handle
+ * has: CMS_NO_COMPACT / CMS_NO_VMM / CMS_NO_FORMS handles load any image. */
+
+/* Bytes cms_save_table would write / cms_save_table_device needs. */
+int cms_checkpoint_size(cms_handle* h, int64_t* bytes);
+/* The image to path: written as path + ".tmp", then renamed, so a crash never
+ * leaves a half file under the real name. */
+int cms_save_table(cms_handle* h, const char* path);
+int cms_load_table(cms_handle* h, const char* path);
+/* The image into / out of device memory on the handle's GPU (16-byte aligned).
+ * *bytes = the image's length; CMS_E_PARAM when capacity is smaller (*bytes is
+ * still set).  Blocking: the image is complete when the call returns. */
+int cms_save_table_device(cms_handle* h, void* d_buf, int64_t capacity, int64_t* bytes);
+int cms_load_table_device(cms_handle* h, const void* d_buf, int64_t bytes);
+/* The parameters a handle needs to load the file (host only: no device call):
+ * depth, width, counter type, seed, num_owners and frac_bits from its header;
+ * weighting unweighted, device -1, flags 0.  CMS_E_PARAM for a file that is
+ * not a checkpoint, has an unknown version, or is shorter or longer than its
+ * header claims.  file_bytes may be NULL. */
+int cms_checkpoint_info(const char* path, cms_params* out, int64_t* file_bytes);
+
 /* ---- instrumentation ------------------------------------------------------- */
 typedef struct cms_stats {
   uint32_t struct_size;     /* sizeof(cms_stats) as the caller compiled it: only fields that fit are written */

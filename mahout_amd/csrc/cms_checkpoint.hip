@@ -1,0 +1,966 @@
+// cms_checkpoint.hip -- checkpoint and restore of the sketch table
+// (cms_save_table / cms_load_table and their device-image twins).
+//
+// The image (cms_checkpoint.h, DESIGN.md 3 "Checkpoint image") carries every
+// owner row in the form the table stores it in -- a list row its 2 + 2 d m
+// bytes, a 4-bit row d w / 2, a hot row its u32 counters -- so a config-3
+// table leaves as the 2.65 GB it occupies, not as 164 GB of dense u32.  Save
+// is a gather of the rows' stored bytes into one dense payload, load a
+// scatter into a freshly laid-out arena (row_layout: no holes left by movers).
+//
+//   k_ckpt_dir     one pass over the owners: directory entry + source address
+//   k_ckpt_pack    segmented copy driven by the DESTINATION: a workgroup takes
+//                  a fixed 16 KB tile of the payload, finds the tile's first
+//                  row by binary search, keeps the tile's row boundaries in
+//                  LDS, and every lane moves 16-byte chunks.  A Zipf table has
+//                  a few 160 KB hot rows and a million rows of about 1 KB: a
+//                  workgroup per row would be unbalanced, a tile per
+//                  workgroup is not.
+//   k_ckpt_unpack  the same mapping in reverse; recomputes the checksum from
+//                  what it read and validates list rows while copying
+//   k_ckpt_expand  a handle without forms (CMS_NO_FORMS=1) receives narrow
+//                  rows expanded to u16
+//
+// The payload offsets are summed on the host from the directory's read-back
+// (64-bit: 16-byte units of a 79 GB arena pass 2^32); the same read-back
+// sizes the image.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "cms_checkpoint.h"
+#include "cms_internal.h"
+
+namespace cms {
+namespace {
+
+using namespace ckpt;
+
+constexpr int kTileChunks = 1024;        // 16-byte chunks per workgroup tile (16 KB)
+constexpr uint64_t kListBit = 1ull << 63;  // seg_len: the segment is a list row (validated by the unpack)
+constexpr uint64_t kIoChunk = 64ull << 20;  // bytes per pinned staging buffer of the file path
+enum : unsigned long long { kBadList = 1, kBadPad = 2 };
+
+// The rows that have stored bytes, in row order: payload byte offsets
+// (off[nseg] = the payload's length), device addresses and lengths.
+struct SegView {
+  const uint64_t* off;   // [nseg + 1]
+  const uint64_t* addr;  // [nseg]
+  const uint64_t* len;   // [nseg] (| kListBit)
+  int64_t nseg;
+};
+
+__global__ void k_ckpt_dir(TableView tv, const uint32_t* cbound, const uint64_t* mass, const double* t64, int64_t n,
+                           int depth, int empty, DirEntry* dir, uint64_t* addr) {
+  const int64_t dw = tv.dw;
+  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
+    DirEntry e;
+    e.form = kRowZero;
+    e.cls = 0;
+    e.rsv = 0;
+    e.cbound = 0;
+    e.len = 0;
+    e.mass = mass[r];
+    e.off = 0;
+    uint64_t a = 0;
+    if (empty) {
+      // every counter is zero (the arrays below are stale)
+    } else if (t64) {
+      e.form = kRowF64;
+      e.len = 8 * (uint64_t)dw;
+      a = reinterpret_cast<uint64_t>(t64 + r * dw);
+    } else {
+      const int32_t s = tv.hidx[r];
+      if (s >= 0) {
+        e.form = kRowHot;
+        e.len = 4 * (uint64_t)dw;
+        a = reinterpret_cast<uint64_t>(tv.hot + (int64_t)s * dw);
+      } else {
+        const int64_t o = tv.off[r];
+        e.cbound = cbound[r];
+        if (o != 0) {  // (offset 0: the shared zero row)
+          e.cls = (uint8_t)(o & kCapMask);
+          a = reinterpret_cast<uint64_t>(tv.t16 + (o & ~kCapMask));
+          if (s == kFormList) {
+            e.form = kRowList;
+            e.len = 2 + 2 * (uint64_t)depth * tv.list_m(r);
+          } else {
+            e.form = s == kFormU1 ? kRowU1 : s == kFormU2 ? kRowU2 : s == kFormU4 ? kRowU4 : s == kFormU8 ? kRowU8 : kRowU16;
+            e.len = ((uint64_t)dw * (uint64_t)form_bits(s)) / 8;
+          }
+        }
+      }
+    }
+    dir[r] = e;
+    addr[r] = a;
+  }
+}
+
+// ---- the tile mapping shared by pack and unpack ----
+
+// The segments of the tile starting at chunk t0: first = the one holding its
+// first byte, s_off[0 .. cnt) their payload offsets (a segment takes at least
+// one chunk, so at most kTileChunks + 1 of them touch a tile).
+__device__ __forceinline__ void tile_setup(const SegView& sv, uint64_t t0, uint64_t* s_off, int64_t& first, int& cnt) {
+  const uint64_t pos = t0 * 16;
+  int64_t lo = 0, hi = sv.nseg;  // first segment starting past pos
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (sv.off[mid] <= pos) lo = mid + 1; else hi = mid;
+  }
+  first = lo - 1;  // (off[0] == 0 <= pos)
+  cnt = (int)min<int64_t>(sv.nseg - first, kTileChunks + 1);
+  for (int i = threadIdx.x; i < cnt; i += blockDim.x) s_off[i] = sv.off[first + i];
+  __syncthreads();
+}
+__device__ __forceinline__ int tile_find(const uint64_t* s_off, int cnt, uint64_t pos) {
+  int lo = 0, hi = cnt;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (s_off[mid] <= pos) lo = mid + 1; else hi = mid;
+  }
+  return lo - 1;
+}
+
+// 16 bytes of a row from p (4-byte aligned), of which rem (> 0, even) belong
+// to the row: the others read as zero.  Arena rows are 128-byte aligned and
+// take whole 128-byte units, so a list's last word is read inside its place;
+// hot and fp64 rows are whole words.
+__device__ __forceinline__ uint4 load16(const uint8_t* p, uint64_t rem) {
+  if (rem >= 16 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) return *reinterpret_cast<const uint4*>(p);
+  const uint32_t* p32 = reinterpret_cast<const uint32_t*>(p);
+  uint32_t w[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    w[k] = (uint64_t)(4 * k) < rem ? p32[k] : 0u;
+    if (rem < 16 && (uint64_t)k == (rem >> 2) && (rem & 3)) w[k] &= (1u << (8 * (uint32_t)(rem & 3))) - 1u;
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+// the first rem (> 0, even) bytes of v to p (4-byte aligned): nothing past the row's end is written
+__device__ __forceinline__ void store16(uint8_t* p, uint64_t rem, const uint4& v) {
+  if (rem >= 16 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+    *reinterpret_cast<uint4*>(p) = v;
+    return;
+  }
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if ((uint64_t)(4 * k + 4) <= rem) reinterpret_cast<uint32_t*>(p)[k] = w[k];
+    else if ((uint64_t)(4 * k + 2) <= rem) *reinterpret_cast<uint16_t*>(p + 4 * k) = (uint16_t)w[k];
+  }
+}
+__device__ __forceinline__ unsigned long long sum16(const uint4& v) {
+  return ((unsigned long long)v.x | ((unsigned long long)v.y << 32)) +
+         ((unsigned long long)v.z | ((unsigned long long)v.w << 32));
+}
+// per-lane sums -> one atomic add per workgroup
+__device__ __forceinline__ void block_add(unsigned long long acc, unsigned long long* s_red, unsigned long long* out) {
+  s_red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) s_red[threadIdx.x] += s_red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && s_red[0]) atomicAdd(out, s_red[0]);
+}
+
+// Payload chunks [c0, c1) -> dst (chunk c0 at dst, 16-byte aligned); out[0] += their checksum.
+__global__ __launch_bounds__(256) void k_ckpt_pack(SegView sv, uint64_t c0, uint64_t c1, uint8_t* dst,
+                                                   unsigned long long* out) {
+  __shared__ uint64_t s_off[kTileChunks + 1];
+  __shared__ unsigned long long s_red[256];
+  unsigned long long acc = 0;
+  const uint64_t tiles = (c1 - c0 + kTileChunks - 1) / kTileChunks;
+  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const uint64_t t0 = c0 + t * kTileChunks, t1 = min<uint64_t>(t0 + (uint64_t)kTileChunks, c1);
+    int64_t first;
+    int cnt;
+    tile_setup(sv, t0, s_off, first, cnt);
+    for (uint64_t c = t0 + threadIdx.x; c < t1; c += 256) {
+      const uint64_t pos = c * 16;
+      const int i = tile_find(s_off, cnt, pos);
+      const int64_t s = first + i;
+      const uint64_t rel = pos - s_off[i];
+      const uint64_t len = sv.len[s] & ~kListBit;
+      uint4 v = make_uint4(0, 0, 0, 0);  // (padding stores zero)
+      if (rel < len) v = load16(reinterpret_cast<const uint8_t*>(sv.addr[s]) + rel, len - rel);
+      *reinterpret_cast<uint4*>(dst + (c - c0) * 16) = v;
+      acc += sum16(v);
+    }
+    __syncthreads();  // the tile's boundaries are read before the next tile's replace them
+  }
+  block_add(acc, s_red, out);
+}
+
+// src (chunk c0 at src) -> the rows' new places; out[0] += the checksum of
+// what was read, out[1] |= kBad*.  A list row's chunk is checked before it is
+// stored: its leading u16 must be the key count its length implies and every
+// entry a bucket (< width) -- the readers index LDS by these entries.  A chunk
+// that fails is not stored.
+__global__ __launch_bounds__(256) void k_ckpt_unpack(SegView sv, uint64_t c0, uint64_t c1, const uint8_t* src, int depth,
+                                                     int width, unsigned long long* out) {
+  __shared__ uint64_t s_off[kTileChunks + 1];
+  __shared__ unsigned long long s_red[256];
+  unsigned long long acc = 0, bad = 0;
+  const uint64_t tiles = (c1 - c0 + kTileChunks - 1) / kTileChunks;
+  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const uint64_t t0 = c0 + t * kTileChunks, t1 = min<uint64_t>(t0 + (uint64_t)kTileChunks, c1);
+    int64_t first;
+    int cnt;
+    tile_setup(sv, t0, s_off, first, cnt);
+    for (uint64_t c = t0 + threadIdx.x; c < t1; c += 256) {
+      const uint64_t pos = c * 16;
+      const int i = tile_find(s_off, cnt, pos);
+      const int64_t s = first + i;
+      const uint64_t rel = pos - s_off[i];
+      const uint64_t lf = sv.len[s];
+      const uint64_t len = lf & ~kListBit;
+      const uint4 v = *reinterpret_cast<const uint4*>(src + (c - c0) * 16);
+      acc += sum16(v);
+      if (rel >= len) {  // (cannot happen with a validated directory)
+        bad |= kBadPad;
+        continue;
+      }
+      const uint64_t rem = len - rel;
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+      bool ok = true;
+      if (rem < 16) {  // pad bytes are zero in a valid image
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+          if ((uint64_t)(2 * q) >= rem && ((w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu)) ok = false;
+        if (!ok) bad |= kBadPad;
+      }
+      if (lf & kListBit) {
+        const uint64_t e0 = rel >> 1, ne = len >> 1;
+        const uint32_t m_want = (uint32_t)((len - 2) / (2 * (uint64_t)depth));
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const uint32_t e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
+          if (e0 + q < ne && (e0 + q == 0 ? e != m_want : e >= (uint32_t)width)) {
+            ok = false;
+            bad |= kBadList;
+          }
+        }
+      }
+      if (ok) store16(reinterpret_cast<uint8_t*>(sv.addr[s]) + rel, rem, v);
+    }
+    __syncthreads();
+  }
+  if (bad) atomicOr(out + 1, bad);
+  block_add(acc, s_red, out);
+}
+
+// One workgroup per listed row: the narrow image at src[i] (a validated copy
+// of its payload bytes) expanded to u16 counters in the row's whole slot,
+// which reset_rows_zero left zeroed.
+__global__ __launch_bounds__(256) void k_ckpt_expand(const int32_t* rows, const uint64_t* src, const int32_t* form,
+                                                     int64_t count, uint16_t* t16, int64_t su, int64_t dw, int w) {
+  for (int64_t i = blockIdx.x; i < count; i += gridDim.x) {
+    const int64_t r = rows[i];
+    const uint8_t* p8 = reinterpret_cast<const uint8_t*>(src[i]);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(t16 + su + r * su);
+    const int32_t f = form[i];
+    if (f == kFormList) {  // the list re-count: entry (sketch row t / m, bucket e) adds one
+      const uint16_t* e = reinterpret_cast<const uint16_t*>(p8);
+      const uint32_t m = e[0];
+      const int64_t ne = (dw / w) * (int64_t)m;
+      for (int64_t t = threadIdx.x; t < ne; t += 256) {
+        const int64_t ci = (t / m) * w + e[1 + t];
+        atomicAdd(dst + (ci >> 1), 1u << ((ci & 1) * 16));  // (a counter stays below 2^16: no carry)
+      }
+    } else {
+      for (int64_t j = (int64_t)threadIdx.x * 16; j < dw; j += 256 * 16) {
+        uint32_t v[16];
+        unpack16(f, p8, j, v);
+        pack16<2>(v, dst, j);
+      }
+    }
+  }
+}
+
+// ---- host side ----
+
+struct Guard {
+  cms_handle* h;
+  explicit Guard(cms_handle* hh) : h(hh) {
+    h->mu.lock();
+    (void)hipSetDevice(h->device);
+  }
+  ~Guard() { h->mu.unlock(); }
+};
+
+struct Image {
+  Header hd;
+  std::vector<int64_t> ids;
+  std::vector<DirEntry> dir;
+  std::vector<uint64_t> addr;  // [n] device address of each row's stored bytes (0: none)
+};
+
+struct Segs {
+  std::vector<uint64_t> off, addr, len;
+  DevBuf d_off, d_addr, d_len;
+  SegView view() const { return SegView{d_off.as<uint64_t>(), d_addr.as<uint64_t>(), d_len.as<uint64_t>(), (int64_t)addr.size()}; }
+  int upload(cms_handle* h) {
+    const size_t k = addr.size();
+    CMS_HIP(d_off.ensure(sizeof(uint64_t) * (k + 1)));
+    CMS_HIP(d_addr.ensure(sizeof(uint64_t) * std::max<size_t>(k, 1)));
+    CMS_HIP(d_len.ensure(sizeof(uint64_t) * std::max<size_t>(k, 1)));
+    CMS_HIP(hipMemcpyAsync(d_off.ptr, off.data(), sizeof(uint64_t) * (k + 1), hipMemcpyHostToDevice, h->stream));
+    if (k) {
+      CMS_HIP(hipMemcpyAsync(d_addr.ptr, addr.data(), sizeof(uint64_t) * k, hipMemcpyHostToDevice, h->stream));
+      CMS_HIP(hipMemcpyAsync(d_len.ptr, len.data(), sizeof(uint64_t) * k, hipMemcpyHostToDevice, h->stream));
+    }
+    CMS_HIP(hipStreamSynchronize(h->stream));
+    return CMS_OK;
+  }
+};
+
+// the rows with stored bytes, from a directory and the rows' device addresses
+void build_segs(const Image& im, Segs& sg) {
+  const int64_t n = im.hd.num_owners;
+  sg.off.clear(), sg.addr.clear(), sg.len.clear();
+  for (int64_t r = 0; r < n; ++r) {
+    const DirEntry& e = im.dir[r];
+    if (e.len == 0) continue;
+    sg.off.push_back(e.off);
+    sg.addr.push_back(im.addr[r]);
+    sg.len.push_back(e.len | (e.form == kRowList ? kListBit : 0));
+  }
+  sg.off.push_back(im.hd.payload_bytes);
+}
+
+unsigned grid_for(cms_handle* h, uint64_t chunks) {
+  const uint64_t tiles = (chunks + kTileChunks - 1) / kTileChunks;
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(tiles, (uint64_t)h->num_cus * 16));
+}
+
+void add_host_time(cms_handle* h, const char* name, std::chrono::steady_clock::time_point t0) {
+  if (!h->timing) return;
+  auto& a = h->timing_acc[name];
+  a.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  a.launches += 1;
+}
+
+int check_saveable(cms_handle* h, const char* what) {
+  if (h->per_owner)
+    return set_error(CMS_E_STATE, "%s: a per-owner-shape handle keeps the DataModel, not a table", what);
+  if (h->multi() && !h->merged)
+    return set_error(CMS_E_STATE, "%s: a multi-rank handle holds the whole table only once merged (cms_finalize)", what);
+  if (h->multi() && h->dlog_n > 0)  // batches the other ranks have not seen, and theirs not applied here
+    return set_error(CMS_E_STATE, "%s: COO batches since the merge are not exchanged yet (cms_finalize)", what);
+  return CMS_OK;
+}
+
+// The image of the handle's table but its payload: header, IDs, directory
+// and each row's source address.
+int plan_save(cms_handle* h, Image& im) {
+  const int64_t n = h->n;
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  DevBuf d_dir, d_addr;
+  CMS_HIP(d_dir.ensure(sizeof(DirEntry) * (size_t)n));
+  CMS_HIP(d_addr.ensure(sizeof(uint64_t) * (size_t)n));
+  {
+    TimedScope ts(h, "ckpt_dir");
+    const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192));
+    hipLaunchKernelGGL(k_ckpt_dir, dim3(g), dim3(256), 0, h->stream, h->tview(), h->d_cbound, h->d_row_mass,
+                       h->f64 ? h->d_t64 : (const double*)nullptr, n, (int)h->p.depth, h->empty ? 1 : 0,
+                       d_dir.as<DirEntry>(), d_addr.as<uint64_t>());
+    CMS_HIP(hipGetLastError());
+  }
+  im.dir.resize((size_t)n);
+  im.addr.resize((size_t)n);
+  CMS_HIP(hipMemcpyAsync(im.dir.data(), d_dir.ptr, sizeof(DirEntry) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipMemcpyAsync(im.addr.data(), d_addr.ptr, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  uint64_t at = 0;
+  for (int64_t r = 0; r < n; ++r) {
+    im.dir[r].off = at;
+    at += round16(im.dir[r].len);
+  }
+  Header& hd = im.hd;
+  std::memset(&hd, 0, sizeof(hd));
+  std::memcpy(hd.magic, kMagic, sizeof(kMagic));
+  hd.version = kVersion;
+  hd.depth = h->p.depth;
+  hd.width = h->p.width;
+  hd.counter_type = h->p.counter_type;
+  hd.frac_bits = h->p.frac_bits;
+  hd.num_owners = n;
+  hd.pairs_ingested = h->pairs_ingested;
+  hd.seed = h->p.seed;
+  im.ids = h->h_owner_ids;
+  hd.flags = im.ids.empty() ? 0 : kFlagOwnerIds;
+  layout_sections(&hd);
+  hd.payload_bytes = at;
+  hd.file_bytes = hd.payload_off + at;
+  for (int i = 0; i < h->p.depth; ++i) {
+    hd.a[i] = h->a[i];
+    hd.b[i] = h->b[i];
+  }
+  // the writer holds itself to the reader's rules
+  if (const char* why = check_directory(hd, im.dir.data(), n))
+    return set_error(CMS_E_STATE, "checkpoint: the table's directory is inconsistent (%s)", why);
+  return CMS_OK;
+}
+
+int pack_range(cms_handle* h, const Segs& sg, uint64_t c0, uint64_t c1, uint8_t* d_dst, unsigned long long* d_out) {
+  if (c1 <= c0) return CMS_OK;
+  TimedScope ts(h, "ckpt_pack");
+  hipLaunchKernelGGL(k_ckpt_pack, dim3(grid_for(h, c1 - c0)), dim3(256), 0, h->stream, sg.view(), c0, c1, d_dst, d_out);
+  CMS_HIP(hipGetLastError());
+  return CMS_OK;
+}
+
+int unpack_range(cms_handle* h, const Segs& sg, uint64_t c0, uint64_t c1, const uint8_t* d_src,
+                 unsigned long long* d_out) {
+  if (c1 <= c0) return CMS_OK;
+  TimedScope ts(h, "ckpt_unpack");
+  hipLaunchKernelGGL(k_ckpt_unpack, dim3(grid_for(h, c1 - c0)), dim3(256), 0, h->stream, sg.view(), c0, c1, d_src,
+                     (int)h->p.depth, (int)h->p.width, d_out);
+  CMS_HIP(hipGetLastError());
+  return CMS_OK;
+}
+
+// two pinned host buffers, two device staging buffers and their events (the file path)
+struct Staging {
+  void* pin[2] = {nullptr, nullptr};
+  DevBuf dev[2];
+  hipEvent_t ev_a[2] = {nullptr, nullptr}, ev_b[2] = {nullptr, nullptr};
+  int init(uint64_t bytes) {
+    for (int i = 0; i < 2; ++i) {
+      CMS_HIP(hipHostMalloc(&pin[i], (size_t)bytes, hipHostMallocDefault));
+      CMS_HIP(dev[i].ensure((size_t)bytes));
+      CMS_HIP(hipEventCreateWithFlags(&ev_a[i], hipEventDisableTiming));
+      CMS_HIP(hipEventCreateWithFlags(&ev_b[i], hipEventDisableTiming));
+    }
+    return CMS_OK;
+  }
+  ~Staging() {
+    (void)hipDeviceSynchronize();
+    for (int i = 0; i < 2; ++i) {
+      if (pin[i]) (void)hipHostFree(pin[i]);
+      if (ev_a[i]) (void)hipEventDestroy(ev_a[i]);
+      if (ev_b[i]) (void)hipEventDestroy(ev_b[i]);
+    }
+  }
+};
+
+struct File {
+  FILE* f = nullptr;
+  ~File() {
+    if (f) std::fclose(f);
+  }
+};
+
+// the half-written path + ".tmp" never outlives a failed save (after the rename there is nothing to remove)
+struct TmpRemover {
+  std::string path;
+  ~TmpRemover() { std::remove(path.c_str()); }
+};
+
+int save_file(cms_handle* h, const char* path) {
+  Image im;
+  int rc = plan_save(h, im);
+  if (rc) return rc;
+  Segs sg;
+  build_segs(im, sg);
+  if ((rc = sg.upload(h))) return rc;
+  DevBuf d_out;
+  CMS_HIP(d_out.ensure(2 * sizeof(unsigned long long)));
+  CMS_HIP(hipMemsetAsync(d_out.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
+  const std::string tmp = std::string(path) + ".tmp";
+  TmpRemover cleanup{tmp};  // (declared before the file: it is closed first)
+  File out;
+  out.f = std::fopen(tmp.c_str(), "wb");
+  if (!out.f) return set_error(CMS_E_PARAM, "cannot open %s for writing", tmp.c_str());
+  const Header& hd = im.hd;
+  bool ok = true;
+  const auto t_io = std::chrono::steady_clock::now();
+  {  // header (its checksum follows the payload), IDs, directory
+    static const char zeros[16] = {};
+    ok = ok && std::fwrite(&hd, sizeof(hd), 1, out.f) == 1;
+    if (!im.ids.empty()) ok = ok && std::fwrite(im.ids.data(), 8, im.ids.size(), out.f) == im.ids.size();
+    const uint64_t gap = hd.dir_off - (hd.ids_off + hd.ids_bytes);
+    if (gap) ok = ok && std::fwrite(zeros, 1, (size_t)gap, out.f) == gap;
+    ok = ok && std::fwrite(im.dir.data(), sizeof(DirEntry), im.dir.size(), out.f) == im.dir.size();
+  }
+  // the payload through two pinned buffers: pack of chunk i + 1 (the handle's
+  // stream) and D2H of chunk i (the side stream) run while the host writes
+  // chunk i - 1
+  const uint64_t total = hd.payload_bytes / 16, per = kIoChunk / 16;
+  const uint64_t nchunks = (total + per - 1) / per;
+  if (ok && nchunks > 0) {
+    Staging st;
+    if ((rc = st.init(std::min(kIoChunk, hd.payload_bytes)))) return rc;
+    for (uint64_t i = 0; i <= nchunks && ok; ++i) {
+      if (i < nchunks) {
+        const int b = (int)(i & 1);
+        const uint64_t c0 = i * per, c1 = std::min(total, c0 + per);
+        if (i >= 2) CMS_HIP(hipStreamWaitEvent(h->stream, st.ev_b[b], 0));  // the copy out of dev[b] is done
+        if ((rc = pack_range(h, sg, c0, c1, st.dev[b].as<uint8_t>(), d_out.as<unsigned long long>()))) return rc;
+        CMS_HIP(hipEventRecord(st.ev_a[b], h->stream));
+        CMS_HIP(hipStreamWaitEvent(h->side_stream, st.ev_a[b], 0));
+        CMS_HIP(hipMemcpyAsync(st.pin[b], st.dev[b].ptr, (size_t)((c1 - c0) * 16), hipMemcpyDeviceToHost, h->side_stream));
+        CMS_HIP(hipEventRecord(st.ev_b[b], h->side_stream));
+      }
+      if (i >= 1) {
+        const uint64_t j = i - 1, c0 = j * per, c1 = std::min(total, c0 + per);
+        CMS_HIP(hipEventSynchronize(st.ev_b[j & 1]));
+        ok = std::fwrite(st.pin[j & 1], 16, (size_t)(c1 - c0), out.f) == c1 - c0;
+      }
+    }
+  }
+  unsigned long long res[2] = {0, 0};
+  CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  im.hd.checksum = res[0];
+  ok = ok && std::fseek(out.f, 0, SEEK_SET) == 0 && std::fwrite(&im.hd, sizeof(im.hd), 1, out.f) == 1;
+  const bool closed = std::fclose(out.f) == 0;
+  out.f = nullptr;
+  add_host_time(h, "ckpt_io", t_io);
+  if (!ok || !closed) return set_error(CMS_E_PARAM, "short write to %s", tmp.c_str());
+  if (std::rename(tmp.c_str(), path) != 0) return set_error(CMS_E_PARAM, "cannot rename %s to %s", tmp.c_str(), path);
+  return CMS_OK;
+}
+
+int save_device(cms_handle* h, void* d_buf, int64_t capacity, int64_t* bytes) {
+  Image im;
+  int rc = plan_save(h, im);
+  if (rc) return rc;
+  *bytes = (int64_t)im.hd.file_bytes;
+  if (!d_buf) return CMS_OK;  // (the size only)
+  if ((uint64_t)capacity < im.hd.file_bytes)
+    return set_error(CMS_E_PARAM, "device image needs %lld bytes, the buffer has %lld", (long long)im.hd.file_bytes,
+                     (long long)capacity);
+  if (reinterpret_cast<uintptr_t>(d_buf) & 15) return set_error(CMS_E_PARAM, "device image must be 16-byte aligned");
+  Segs sg;
+  build_segs(im, sg);
+  if ((rc = sg.upload(h))) return rc;
+  DevBuf d_out;
+  CMS_HIP(d_out.ensure(2 * sizeof(unsigned long long)));
+  CMS_HIP(hipMemsetAsync(d_out.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
+  uint8_t* base = static_cast<uint8_t*>(d_buf);
+  const Header& hd = im.hd;
+  if ((rc = pack_range(h, sg, 0, hd.payload_bytes / 16, base + hd.payload_off, d_out.as<unsigned long long>()))) return rc;
+  unsigned long long res[2] = {0, 0};
+  CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  im.hd.checksum = res[0];
+  // header, IDs (and the gap before the directory), directory
+  std::vector<uint8_t> head((size_t)hd.payload_off, 0);
+  std::memcpy(head.data(), &im.hd, sizeof(im.hd));
+  if (!im.ids.empty()) std::memcpy(head.data() + hd.ids_off, im.ids.data(), (size_t)hd.ids_bytes);
+  std::memcpy(head.data() + hd.dir_off, im.dir.data(), (size_t)hd.dir_bytes);
+  CMS_HIP(hipMemcpyAsync(base, head.data(), head.size(), hipMemcpyHostToDevice, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  return CMS_OK;
+}
+
+// ---- load ----
+
+int check_loadable(cms_handle* h, const char* what) {
+  if (h->per_owner)
+    return set_error(CMS_E_STATE, "%s: a per-owner-shape handle keeps the DataModel, not a table", what);
+  if (h->comm || h->ext_comm || h->multi())
+    return set_error(CMS_E_STATE, "%s: the handle has a communicator (the merge would sum every rank's copy)", what);
+  if (!h->empty || h->pairs_ingested != 0)
+    return set_error(CMS_E_STATE, "%s: the handle must be empty (new, or after cms_reset)", what);
+  return CMS_OK;
+}
+
+int check_matches(cms_handle* h, const Header& hd) {
+  if (hd.depth != h->p.depth || hd.width != h->p.width)
+    return set_error(CMS_E_PARAM, "checkpoint shape d=%d w=%d, handle d=%d w=%d", hd.depth, hd.width, h->p.depth, h->p.width);
+  if (hd.num_owners != h->n)
+    return set_error(CMS_E_PARAM, "checkpoint of %lld owners, handle of %lld", (long long)hd.num_owners, (long long)h->n);
+  if (hd.counter_type != h->p.counter_type) return set_error(CMS_E_PARAM, "checkpoint and handle differ in counter type");
+  if (hd.frac_bits != h->p.frac_bits)
+    return set_error(CMS_E_PARAM, "checkpoint frac_bits %d, handle %d", hd.frac_bits, h->p.frac_bits);
+  return CMS_OK;
+}
+
+// header, IDs and directory of an image from its first payload_off bytes
+int parse_head(const uint8_t* head, Image& im) {
+  const Header& hd = im.hd;
+  const int64_t n = hd.num_owners;
+  if (hd.flags & kFlagOwnerIds) {
+    im.ids.resize((size_t)n);
+    std::memcpy(im.ids.data(), head + hd.ids_off, (size_t)hd.ids_bytes);
+    if (const char* why = check_owner_ids(im.ids.data(), n)) return set_error(CMS_E_PARAM, "checkpoint: %s", why);
+  }
+  im.dir.resize((size_t)n);
+  std::memcpy(im.dir.data(), head + hd.dir_off, (size_t)hd.dir_bytes);
+  if (const char* why = check_directory(hd, im.dir.data(), n)) return set_error(CMS_E_PARAM, "checkpoint: %s", why);
+  return CMS_OK;
+}
+
+// rows a handle without forms receives expanded to u16 (k_ckpt_expand)
+struct Expand {
+  std::vector<int32_t> rows, form;
+  std::vector<uint64_t> src;
+  DevBuf scratch, d_rows, d_form, d_src;
+};
+
+int32_t table_form(uint8_t f) {
+  return f == kRowList ? kFormList : f == kRowU1 ? kFormU1 : f == kRowU2 ? kFormU2 : f == kRowU4 ? kFormU4
+       : f == kRowU8 ? kFormU8 : kFormU16;
+}
+
+// Lays the validated directory's rows out in the (empty) handle: forms,
+// bounds, masses, hot slots and arena places; im.addr[r] = where row r's
+// stored bytes go.
+int restore_layout(cms_handle* h, Image& im, Expand& ex) {
+  const int64_t n = h->n, dw = h->dw;
+  im.addr.assign((size_t)n, 0);
+  std::vector<uint64_t> mass((size_t)n);
+  for (int64_t r = 0; r < n; ++r) mass[r] = im.dir[r].mass;
+  if (h->f64) {
+    bool any_zero = false;
+    for (int64_t r = 0; r < n; ++r) {
+      any_zero |= im.dir[r].form == kRowZero;
+      if (im.dir[r].form == kRowF64) im.addr[r] = reinterpret_cast<uint64_t>(h->d_t64 + r * dw);
+    }
+    if (any_zero) CMS_HIP(hipMemsetAsync(h->d_t64, 0, sizeof(double) * (size_t)n * (size_t)dw, h->stream));
+    CMS_HIP(hipMemcpyAsync(h->d_row_mass, mass.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    CMS_HIP(hipStreamSynchronize(h->stream));
+    return CMS_OK;
+  }
+  int rc = reset_rows_zero(h);  // every row narrow and zero, no hot slots
+  if (rc) return rc;
+  const int64_t su = slot_units(dw);
+  std::vector<int32_t> hidx((size_t)n);
+  std::vector<uint32_t> cb((size_t)n), caps((size_t)n, 0);
+  std::vector<uint64_t> xoff;
+  int64_t nhot = 0;
+  uint64_t xbytes = 0;
+  for (int64_t r = 0; r < n; ++r) {
+    const DirEntry& e = im.dir[r];
+    cb[r] = e.cbound;
+    if (e.form == kRowHot) {
+      hidx[r] = (int32_t)nhot++;  // the next hot slot in row order
+      continue;
+    }
+    if (e.form == kRowZero) {
+      hidx[r] = kFormU16;
+      continue;
+    }
+    const bool expand = !h->forms_ok && e.form != kRowU16;  // a form this handle cannot hold
+    hidx[r] = expand ? kFormU16 : table_form(e.form);
+    if (expand) {
+      ex.rows.push_back((int32_t)r);
+      ex.form.push_back(table_form(e.form));
+      xoff.push_back(xbytes);
+      xbytes += round16(e.len);
+    }
+    // the row's capacity: its saved place class, and at least its stored bytes
+    // (a byte-class list's place is sized by the list, not by a class)
+    const int64_t units = std::max<int64_t>(class_units(e.cls, dw), ((int64_t)e.len + 1) / 2);
+    caps[r] = (uint32_t)((units + kRowAlign - 1) / kRowAlign);
+  }
+  if ((rc = grow_hot(h, nhot))) return rc;
+  h->hot_used = nhot;
+  CMS_HIP(hipMemcpyAsync(h->d_hidx, hidx.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  CMS_HIP(hipMemcpyAsync(h->d_cbound, cb.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  CMS_HIP(hipMemcpyAsync(h->d_row_mass, mass.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  std::vector<int64_t> off((size_t)n);
+  if (h->compact) {  // through row_layout: class_of_units re-derives each place's class
+    CMS_HIP(h->ws_layout.ensure(sizeof(uint32_t) * (size_t)(2 * n + n / 4096 + 16)));
+    uint32_t* d_caps = h->ws_layout.as<uint32_t>();
+    CMS_HIP(hipMemcpyAsync(d_caps, caps.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    if ((rc = row_layout(h, d_caps, d_caps + n))) return rc;
+    CMS_HIP(hipMemcpyAsync(off.data(), h->d_off, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  } else {  // whole slots at the identity offsets
+    for (int64_t r = 0; r < n; ++r) off[r] = (su + r * su) | kCapU16;
+  }
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  if (!ex.rows.empty()) CMS_HIP(ex.scratch.ensure((size_t)xbytes));
+  size_t xi = 0;
+  for (int64_t r = 0; r < n; ++r) {
+    const DirEntry& e = im.dir[r];
+    if (e.len == 0) continue;
+    if (e.form == kRowHot) {
+      im.addr[r] = reinterpret_cast<uint64_t>(h->hot_tab.as<uint32_t>() + (int64_t)hidx[r] * dw);
+    } else if (xi < ex.rows.size() && ex.rows[xi] == r) {
+      ex.src.push_back(reinterpret_cast<uint64_t>(ex.scratch.as<uint8_t>() + xoff[xi]));
+      im.addr[r] = ex.src.back();
+      ++xi;
+    } else {
+      im.addr[r] = reinterpret_cast<uint64_t>(h->d_t16 + (off[r] & ~kCapMask));
+    }
+  }
+  return CMS_OK;
+}
+
+int run_expand(cms_handle* h, Expand& ex) {
+  const size_t k = ex.rows.size();
+  if (k == 0) return CMS_OK;
+  CMS_HIP(ex.d_rows.ensure(sizeof(int32_t) * k));
+  CMS_HIP(ex.d_form.ensure(sizeof(int32_t) * k));
+  CMS_HIP(ex.d_src.ensure(sizeof(uint64_t) * k));
+  CMS_HIP(hipMemcpyAsync(ex.d_rows.ptr, ex.rows.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, h->stream));
+  CMS_HIP(hipMemcpyAsync(ex.d_form.ptr, ex.form.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, h->stream));
+  CMS_HIP(hipMemcpyAsync(ex.d_src.ptr, ex.src.data(), sizeof(uint64_t) * k, hipMemcpyHostToDevice, h->stream));
+  TimedScope ts(h, "ckpt_unpack");
+  hipLaunchKernelGGL(k_ckpt_expand, dim3((unsigned)std::min<size_t>(k, 65536)), dim3(256), 0, h->stream,
+                     ex.d_rows.as<int32_t>(), ex.d_src.as<uint64_t>(), ex.d_form.as<int32_t>(), (int64_t)k, h->d_t16,
+                     slot_units(h->dw), h->dw, (int)h->p.width);
+  CMS_HIP(hipGetLastError());
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  return CMS_OK;
+}
+
+// a refused or failed load leaves the handle as cms_reset does
+int leave_empty(cms_handle* h) {
+  (void)hipStreamSynchronize(h->side_stream);
+  CMS_HIP(hipMemsetAsync(h->d_row_mass, 0, sizeof(uint64_t) * (size_t)h->n, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  h->empty = true;
+  h->norms_valid = false;
+  h->finalized = false;
+  h->pairs_ingested = 0;
+  h->merged = false;
+  h->rf_valid = false;
+  return CMS_OK;
+}
+
+// the verified image becomes the handle's table: "ingested, not finalized"
+int commit_load(cms_handle* h, const Image& im, Expand& ex, const unsigned long long res[2]) {
+  if (res[1] & kBadList) {
+    (void)leave_empty(h);
+    return set_error(CMS_E_PARAM, "checkpoint: a list row's key count or an entry is out of range");
+  }
+  if (res[1] & kBadPad) {
+    (void)leave_empty(h);
+    return set_error(CMS_E_PARAM, "checkpoint: padding bytes are not zero");
+  }
+  if (res[0] != im.hd.checksum) {
+    (void)leave_empty(h);
+    return set_error(CMS_E_PARAM, "checkpoint: payload checksum mismatch");
+  }
+  int rc = run_expand(h, ex);
+  if (rc) {
+    (void)leave_empty(h);
+    return rc;
+  }
+  const Header& hd = im.hd;
+  for (int i = 0; i < h->p.depth; ++i) {  // as cms_set_hash_params installs them
+    h->a[i] = hd.a[i];
+    h->b[i] = hd.b[i];
+    h->hp.ap[i] = reduce_key(hd.a[i]);
+    h->hp.bp[i] = reduce_key(hd.b[i]);
+  }
+  hash_finish(h->hp);
+  h->p.seed = hd.seed;
+  if (!im.ids.empty()) {  // as cms_set_owner_ids
+    if (!h->d_owner_ids) CMS_HIP(hipMalloc(&h->d_owner_ids, sizeof(int64_t) * (size_t)h->n));
+    CMS_HIP(hipMemcpy(h->d_owner_ids, im.ids.data(), sizeof(int64_t) * (size_t)h->n, hipMemcpyHostToDevice));
+    h->h_owner_ids = im.ids;
+  } else if (!h->h_owner_ids.empty()) {  // the saved table's owners are its rows
+    h->h_owner_ids.clear();
+    if (h->d_owner_ids) (void)hipFree(h->d_owner_ids);
+    h->d_owner_ids = nullptr;
+  }
+  h->pairs_ingested = hd.pairs_ingested;
+  h->empty = false;
+  h->norms_valid = false;
+  h->finalized = false;
+  h->mfma_ready = false;
+  h->i8blk_ready = false;
+  h->rf_valid = false;
+  h->merged = false;
+  h->ext_merged = false;
+  h->dlog_n = 0;
+  h->stale_possible = true;
+  return CMS_OK;
+}
+
+int load_file(cms_handle* h, const char* path) {
+  int rc = check_loadable(h, "cms_load_table");
+  if (rc) return rc;
+  File in;
+  in.f = std::fopen(path, "rb");
+  if (!in.f) return set_error(CMS_E_PARAM, "cannot open %s", path);
+  Image im;
+  if (std::fseek(in.f, 0, SEEK_END) != 0) return set_error(CMS_E_PARAM, "cannot seek in %s", path);
+  const long long size = (long long)std::ftell(in.f);
+  std::rewind(in.f);
+  if (size < (long long)sizeof(Header) || std::fread(&im.hd, sizeof(Header), 1, in.f) != 1)
+    return set_error(CMS_E_PARAM, "checkpoint %s: shorter than a checkpoint header", path);
+  if (const char* why = check_header(im.hd, (uint64_t)size)) return set_error(CMS_E_PARAM, "checkpoint %s: %s", path, why);
+  if ((rc = check_matches(h, im.hd))) return rc;
+  const Header& hd = im.hd;
+  {
+    std::vector<uint8_t> head((size_t)hd.payload_off);
+    std::rewind(in.f);
+    if (std::fread(head.data(), 1, head.size(), in.f) != head.size())
+      return set_error(CMS_E_PARAM, "checkpoint %s: short read", path);
+    if ((rc = parse_head(head.data(), im))) return rc;
+  }
+  // ---- every host check has passed: the device part ----
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  Expand ex;
+  Segs sg;
+  DevBuf d_out;
+  unsigned long long res[2] = {0, 0};
+  auto device_part = [&]() -> int {
+    int r = restore_layout(h, im, ex);
+    if (r) return r;
+    build_segs(im, sg);
+    if ((r = sg.upload(h))) return r;
+    CMS_HIP(d_out.ensure(2 * sizeof(unsigned long long)));
+    CMS_HIP(hipMemsetAsync(d_out.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
+    // the mirror of save_file: the host reads chunk i + 1 while chunk i goes
+    // H2D (side stream) and is scattered (the handle's stream)
+    const uint64_t total = hd.payload_bytes / 16, per = kIoChunk / 16;
+    const uint64_t nchunks = (total + per - 1) / per;
+    if (nchunks > 0) {
+      Staging st;
+      if ((r = st.init(std::min(kIoChunk, hd.payload_bytes)))) return r;
+      const auto t_io = std::chrono::steady_clock::now();
+      for (uint64_t i = 0; i < nchunks; ++i) {
+        const int b = (int)(i & 1);
+        const uint64_t c0 = i * per, c1 = std::min(total, c0 + per);
+        if (i >= 2) CMS_HIP(hipEventSynchronize(st.ev_a[b]));  // pin[b] has left the host
+        if (std::fread(st.pin[b], 16, (size_t)(c1 - c0), in.f) != c1 - c0)
+          return set_error(CMS_E_PARAM, "checkpoint %s: short read", path);
+        if (i >= 2) CMS_HIP(hipStreamWaitEvent(h->side_stream, st.ev_b[b], 0));  // dev[b] has been scattered
+        CMS_HIP(hipMemcpyAsync(st.dev[b].ptr, st.pin[b], (size_t)((c1 - c0) * 16), hipMemcpyHostToDevice, h->side_stream));
+        CMS_HIP(hipEventRecord(st.ev_a[b], h->side_stream));
+        CMS_HIP(hipStreamWaitEvent(h->stream, st.ev_a[b], 0));
+        if ((r = unpack_range(h, sg, c0, c1, st.dev[b].as<uint8_t>(), d_out.as<unsigned long long>()))) return r;
+        CMS_HIP(hipEventRecord(st.ev_b[b], h->stream));
+      }
+      CMS_HIP(hipStreamSynchronize(h->stream));
+      add_host_time(h, "ckpt_io", t_io);
+    }
+    CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+    CMS_HIP(hipStreamSynchronize(h->stream));
+    return CMS_OK;
+  };
+  if ((rc = device_part())) {
+    (void)leave_empty(h);
+    return rc;
+  }
+  return commit_load(h, im, ex, res);
+}
+
+int load_device(cms_handle* h, const void* d_buf, int64_t bytes) {
+  int rc = check_loadable(h, "cms_load_table_device");
+  if (rc) return rc;
+  if (bytes < (int64_t)sizeof(Header)) return set_error(CMS_E_PARAM, "checkpoint image: shorter than a checkpoint header");
+  if (reinterpret_cast<uintptr_t>(d_buf) & 15) return set_error(CMS_E_PARAM, "device image must be 16-byte aligned");
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  Image im;
+  CMS_HIP(hipMemcpy(&im.hd, d_buf, sizeof(Header), hipMemcpyDeviceToHost));
+  if (const char* why = check_header(im.hd, (uint64_t)bytes)) return set_error(CMS_E_PARAM, "checkpoint image: %s", why);
+  if ((rc = check_matches(h, im.hd))) return rc;
+  const Header& hd = im.hd;
+  {
+    std::vector<uint8_t> head((size_t)hd.payload_off);
+    CMS_HIP(hipMemcpy(head.data(), d_buf, head.size(), hipMemcpyDeviceToHost));
+    if (std::memcmp(head.data(), &im.hd, sizeof(Header)) != 0)
+      return set_error(CMS_E_PARAM, "checkpoint image changed while it was read");
+    if ((rc = parse_head(head.data(), im))) return rc;
+  }
+  Expand ex;
+  Segs sg;
+  DevBuf d_out;
+  unsigned long long res[2] = {0, 0};
+  auto device_part = [&]() -> int {
+    int r = restore_layout(h, im, ex);
+    if (r) return r;
+    build_segs(im, sg);
+    if ((r = sg.upload(h))) return r;
+    CMS_HIP(d_out.ensure(2 * sizeof(unsigned long long)));
+    CMS_HIP(hipMemsetAsync(d_out.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
+    if ((r = unpack_range(h, sg, 0, hd.payload_bytes / 16, static_cast<const uint8_t*>(d_buf) + hd.payload_off,
+                          d_out.as<unsigned long long>())))
+      return r;
+    CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+    CMS_HIP(hipStreamSynchronize(h->stream));
+    return CMS_OK;
+  };
+  if ((rc = device_part())) {
+    (void)leave_empty(h);
+    return rc;
+  }
+  return commit_load(h, im, ex, res);
+}
+
+}  // namespace
+}  // namespace cms
+
+using namespace cms;
+
+extern "C" {
+
+int cms_checkpoint_size(cms_handle* h, int64_t* bytes) {
+  if (!h || !bytes) return set_error(CMS_E_PARAM, "null argument");
+  if (int rc = cms_synchronize(h)) return rc;
+  Guard g(h);
+  if (int rc = check_saveable(h, "cms_checkpoint_size")) return rc;
+  return save_device(h, nullptr, 0, bytes);
+}
+
+int cms_save_table(cms_handle* h, const char* path) {
+  if (!h || !path) return set_error(CMS_E_PARAM, "null argument");
+  if (int rc = cms_synchronize(h)) return rc;  // a pending device-ingest error: nothing is written
+  Guard g(h);
+  if (int rc = check_saveable(h, "cms_save_table")) return rc;
+  return save_file(h, path);
+}
+
+int cms_save_table_device(cms_handle* h, void* d_buf, int64_t capacity, int64_t* bytes) {
+  if (!h || !d_buf || !bytes) return set_error(CMS_E_PARAM, "null argument");
+  if (int rc = cms_synchronize(h)) return rc;
+  Guard g(h);
+  if (int rc = check_saveable(h, "cms_save_table_device")) return rc;
+  return save_device(h, d_buf, capacity, bytes);
+}
+
+int cms_load_table(cms_handle* h, const char* path) {
+  if (!h || !path) return set_error(CMS_E_PARAM, "null argument");
+  Guard g(h);
+  return load_file(h, path);
+}
+
+int cms_load_table_device(cms_handle* h, const void* d_buf, int64_t bytes) {
+  if (!h || !d_buf) return set_error(CMS_E_PARAM, "null argument");
+  Guard g(h);
+  return load_device(h, d_buf, bytes);
+}
+
+int cms_checkpoint_info(const char* path, cms_params* out, int64_t* file_bytes) {
+  if (!path || !out) return set_error(CMS_E_PARAM, "null argument");
+  File in;
+  in.f = std::fopen(path, "rb");
+  if (!in.f) return set_error(CMS_E_PARAM, "cannot open %s", path);
+  Header hd;
+  if (std::fseek(in.f, 0, SEEK_END) != 0) return set_error(CMS_E_PARAM, "cannot seek in %s", path);
+  const long long size = (long long)std::ftell(in.f);
+  std::rewind(in.f);
+  if (size < (long long)sizeof(Header) || std::fread(&hd, sizeof(Header), 1, in.f) != 1)
+    return set_error(CMS_E_PARAM, "checkpoint %s: shorter than a checkpoint header", path);
+  if (const char* why = check_header(hd, (uint64_t)size)) return set_error(CMS_E_PARAM, "checkpoint %s: %s", path, why);
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(cms_params);
+  out->depth = hd.depth;
+  out->width = hd.width;
+  out->counter_type = hd.counter_type;
+  out->seed = hd.seed;
+  out->num_owners = hd.num_owners;
+  out->weighting = CMS_UNWEIGHTED;  // (an instance property, not the table's)
+  out->device = -1;
+  out->frac_bits = hd.frac_bits;
+  out->flags = 0;
+  if (file_bytes) *file_bytes = (int64_t)hd.file_bytes;
+  return CMS_OK;
+}
+
+}  // extern "C"

@@ -474,6 +474,8 @@ int local_norms(cms_handle* h);
 // round trip: that many slots are reserved and claimed on the device).
 int promote_rows(cms_handle* h, const uint64_t* d_bound, const uint8_t* d_force, bool copy_old, int64_t max_new = -1,
                  uint64_t whole_bound = 0);
+// the hot slot table holds at least `need` rows (live slots are copied over)
+int grow_hot(cms_handle* h, int64_t need);
 // rows holding a u32 slot (synchronises the stream)
 int count_hot_rows(cms_handle* h, int64_t* out);
 // rows per storage form: [0] hot, [1] u16, [2] u8, [3] nibble (synchronises)

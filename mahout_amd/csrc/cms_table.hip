@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void k_promote_rows(const int32_t* list, int64
   }
 }
 
-static int grow_hot(cms_handle* h, int64_t need) {
+int grow_hot(cms_handle* h, int64_t need) {
   if (need <= h->hot_cap) return CMS_OK;
   {  // grow: new slot table, live slots copied over
     // at least `need` (reserved-but-unclaimed slots can make it exceed n)

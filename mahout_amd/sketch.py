@@ -525,6 +525,58 @@ class SketchTable:
             check(self._lib.cms_release_to_stream(self._h, ctypes.c_void_p(s)))
         return out
 
+    # -- checkpoint and restore (DESIGN.md 3 "Checkpoint image") --
+    def checkpoint_size(self):
+        """Bytes save() would write / save_device() returns (cms_checkpoint_size)."""
+        b = ctypes.c_int64()
+        check(self._lib.cms_checkpoint_size(self._h, ctypes.byref(b)))
+        return int(b.value)
+
+    def save(self, path):
+        """The table as a checkpoint file: every row in its stored form
+        (cms_save_table; written as path + ".tmp", then renamed)."""
+        check(self._lib.cms_save_table(self._h, os.fsencode(path)))
+
+    def load(self, path):
+        """A checkpoint file into this (empty) handle; finalize() afterwards
+        derives the norms (cms_load_table)."""
+        check(self._lib.cms_load_table(self._h, os.fsencode(path)))
+
+    def save_device(self):
+        """The checkpoint image as a torch uint8 tensor on the handle's device
+        (cms_save_table_device): the same bytes save() writes."""
+        import torch
+        size = self.checkpoint_size()
+        out = torch.empty(size, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(out.device).synchronize()  # (the allocation is the tensor's alone)
+        b = ctypes.c_int64()
+        check(self._lib.cms_save_table_device(self._h, ctypes.c_void_p(out.data_ptr()), size, ctypes.byref(b)))
+        return out[:b.value]
+
+    def load_device(self, image):
+        """A checkpoint image (uint8 tensor on the handle's device) into this
+        (empty) handle (cms_load_table_device)."""
+        import torch
+        if image.device != torch.device("cuda", self.device) or image.dtype != torch.uint8 or not image.is_contiguous():
+            raise ValueError("image must be a contiguous uint8 tensor on cuda:%d" % self.device)
+        torch.cuda.current_stream(image.device).synchronize()  # its producers are done
+        check(self._lib.cms_load_table_device(self._h, ctypes.c_void_p(image.data_ptr()), int(image.numel())))
+
+    @classmethod
+    def from_checkpoint(cls, path, device=-1, weighted=False):
+        """A new handle of the file's shape (cms_checkpoint_info), loaded from it."""
+        lib = _lib.load()
+        p = _lib.CmsParams()
+        check(lib.cms_checkpoint_info(os.fsencode(path), ctypes.byref(p), None))
+        t = cls(p.num_owners, depth=p.depth, width=p.width, seed=p.seed, weighted=weighted, device=device,
+                frac_bits=p.frac_bits, counters="f64" if p.counter_type == _lib.CMS_COUNTER_F64 else "u32")
+        try:
+            t.load(path)
+        except Exception:
+            t.close()
+            raise
+        return t
+
     def release_scratch(self):
         """cms_release_scratch: ingest/query scratch and the kept refresh lists
         go back to the allocator (the next refresh is a whole job)."""

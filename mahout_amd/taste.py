@@ -141,10 +141,17 @@ class CosineCM:
     itemSimilarity are the sketch-cosine ItemSimilarity.
     """
 
-    def __init__(self, dataModel, conf, hfBuilder, weighting=Weighting.UNWEIGHTED, device=-1):
+    def __init__(self, dataModel, conf, hfBuilder, weighting=Weighting.UNWEIGHTED, device=-1, sketches=None):
+        """sketches: a checkpoint file written by saveSketches(); the sketches
+        are loaded from it instead of being built from the DataModel (fixed
+        shapes only; the file's shape, owners and counter type must be the
+        ones this DataModel and conf would build)."""
         if not dataModel.hasPreferenceValues():  # CosineCM.java:38
             raise ValueError("DataModel doesn't have preference values")
         self._per_owner = isinstance(conf, CountMinSketchConfig)
+        if sketches is not None and self._per_owner:
+            raise ValueError("sketches= needs a fixed-shape configuration (per-owner shapes keep the DataModel)")
+        self._sketches = sketches
         if self._per_owner:
             width = depth = None  # each owner has its own shape
         else:
@@ -172,7 +179,10 @@ class CosineCM:
                 self._table = SketchTable(m.getNumUsers(), depth=self.depth, width=self.width, seed=self._hfb.seed,
                                           weighted=self._weighted, device=self._device, owner_ids=m.getUserIDs(),
                                           frac_bits=fb, counters=counters)
-                self._table.ingest_csr(m.offsets, m.keys, m.values)
+                if self._sketches is not None:
+                    self._table.load(self._sketches)  # (installs the file's hash parameters and owner IDs)
+                else:
+                    self._table.ingest_csr(m.offsets, m.keys, m.values)
             self._table.finalize()
         except _lib.CmsError as e:
             raise _map_error(e)
@@ -236,7 +246,18 @@ class CosineCM:
     def refresh(self, alreadyRefreshed=None):
         """Refreshable.refresh: rebuild every sketch from the data model."""
         self._table.close()
+        self._sketches = None  # (a refresh reads the DataModel, as the reference's does)
         self._build()
+
+    def saveSketches(self, path):
+        """Every owner's sketch as one checkpoint file (SketchTable.save);
+        CosineCM(..., sketches=path) loads it instead of ingesting."""
+        if self._per_owner:
+            raise ValueError("saveSketches needs a fixed-shape configuration")
+        try:
+            self._table.save(path)
+        except _lib.CmsError as e:
+            raise _map_error(e)
 
     def close(self):
         self._table.close()
