@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "cms_device.h"
 #include "cms_internal.h"
@@ -923,12 +924,71 @@ __device__ __forceinline__ void mid_rows(
   }
 }
 
+// The branch-free row hash (RowHash) in k_build_slices and mid_streamed; the
+// bound-analysis hashes live in each_bucket, so those builds keep it.
+#if defined(CMS_BUILD_CHEAPHASH) || defined(CMS_BUILD_GATHERHASH)
+constexpr bool kRowHash = false;
+#else
+constexpr bool kRowHash = true;
+#endif
+
+// One pass of a workgroup of T threads over the keys [lo, end), PER keys a
+// thread a step: the next step's loads (load(i), a raw key of type R) are
+// issued before this step's keys go to f, so a load's latency hides behind
+// the previous keys' hashes and LDS adds.  f runs for live keys only (a raw
+// key may be any value) and returns whether the key is still to be done: those
+// keys go to g after the step's last f, in a rolled loop, so the rare route's
+// code stands once and outside the unrolled keys (NoRedo for g: f does every
+// key itself, its answer is not read).
+struct NoRedo {};
+template <typename R, int PER, int T, typename L, typename F, typename G>
+__device__ __forceinline__ void key_pass(int64_t lo, int64_t end, int tid, L&& load, F&& f, G&& g) {
+  constexpr int64_t kStep = (int64_t)PER * T;
+  R nx[PER];
+  auto fetch = [&](int64_t base) {
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int64_t i = base + tid + (int64_t)u * T;
+      nx[u] = i < end ? load(i) : R(0);
+    }
+  };
+  if (lo < end) fetch(lo);
+  for (int64_t base = lo; base < end; base += kStep) {
+    R kk[PER];
+#pragma unroll
+    for (int u = 0; u < PER; ++u) kk[u] = nx[u];
+    if (base + kStep < end) fetch(base + kStep);
+    const int live = (int)min(end - base, kStep);  // (uniform) keys of this step
+    if constexpr (std::is_same<typename std::decay<G>::type, NoRedo>::value) {
+#pragma unroll
+      for (int u = 0; u < PER; ++u)
+        if (tid < live - u * T) f(kk[u]);
+    } else {
+      uint32_t left = 0;
+#pragma unroll
+      for (int u = 0; u < PER; ++u)
+        if (tid < live - u * T && f(kk[u])) left |= 1u << u;
+      if (left) {
+#pragma unroll 1
+        for (int u = 0; u < PER; ++u) {
+          if (!((left >> u) & 1u)) continue;
+          R k = kk[0];
+#pragma unroll
+          for (int j = 1; j < PER; ++j) k = j == u ? kk[j] : k;
+          g(k);
+        }
+      }
+    }
+  }
+}
+
 // STREAMED mid owners (more than kMidCachedKeys keys) of a unit-increment
 // build: ONE key pass for all d sketch rows, the shape of k_build_slices on a
 // [d][w] u8 image (d*w bytes, 40 KB at config 3).  mid_rows walks such an
 // owner's keys d times, one sketch row each, every step's loads waited for
-// before its keys are hashed; here the tokens are fetched a step ahead,
-// resolved once per key and hashed by each_bucket<D>.  512 threads per image:
+// before its keys are hashed; here the tokens are fetched a step ahead and
+// each key is hashed once for all d rows (RowHash, or each_bucket where it
+// does not apply).  512 threads per image:
 // four images fill a CU's LDS, and with 256 threads they were 16 waves per CU
 // (the k_build_image experiment, which also swept its image for the few
 // hundred keys of a cached owner); four 512-thread workgroups are the CU's
@@ -982,30 +1042,49 @@ __device__ __forceinline__ void mid_streamed(const int64_t* lo_, const int64_t* 
     if (u8_start) {
       for (int j = tid; j < depth * nq; j += T) l4[j] = make_uint4(0, 0, 0, 0);
       __syncthreads();
-      constexpr int64_t kStep = (int64_t)kStreamPer * T;
-      uint64_t nx[kStreamPer];
-      auto fetch = [&](int64_t base) {
-#pragma unroll
-        for (int u = 0; u < kStreamPer; ++u) {
-          const int64_t i = base + tid + (int64_t)u * T;
-          nx[u] = i < hi ? keys.raw(i) : 0ULL;
-        }
+      auto add = [&](int r, uint32_t bk) {
+        const uint32_t c = (uint32_t)r * (uint32_t)w + bk;
+        atomicAdd(&lds[c >> 2], 1u << ((c & 3u) << 3));
       };
-      fetch(lo);
-      for (int64_t base = lo; base < hi; base += kStep) {
-        uint64_t kk[kStreamPer];
+      // k_build_slices' key pass on the u8 image: a key's D rows by RowHash
+      // (cms_hash.h), then its D adds back to back -- the word of counter
+      // (r, bk) is at byte r * w + (bk & ~3) (w % 32 == 0), the shift of its
+      // byte takes the low five bits of bk << 3.  RowHash's constants stay
+      // scalar here: in vector registers the kernel spilled at its 64 VGPRs,
+      // and so it did with a key pass of its own for tokens, for CSR keys or
+      // for the shapes RowHash does not cover -- ONE pass, the three routes
+      // behind scalar branches per key (the last with its rows rolled).
+      constexpr int DR = D > 0 ? D : 1;
+      const RowHash<DR> rh(hp);
+      const bool fast = kRowHash && D > 0 && hp.fastq, tok = keys.tok != nullptr;  // (kernel-uniform)
+      key_pass<uint64_t, kStreamPer, T>(
+          lo, hi, tid, [&](int64_t i) { return keys.raw(i); },
+          [&](uint64_t raw) {
+            if (!fast) {  // any depth, any width
+              each_bucket<(kRowHash ? 0 : D)>(hp, keys.resolve(raw), add);
+              return false;
+            }
+            uint32_t bk[DR];
+            uint32_t k = (uint32_t)raw;    // a token below kTokEscape is the reduced key
+            bool again = k >= kTokEscape;  // (an escaped one is resolved in the redo)
+            if (!tok) {
+              const uint64_t kp = reduce_key((int64_t)raw);
+              k = (uint32_t)kp;
+              again = kp >= kRowHashKeyEnd;
+            }
+            if (rh.rows32(k, bk) || again) {  // the redo: about 1 key in 6,500, and every key that is no u32
+              const uint64_t kp = keys.resolve(raw);
+#pragma unroll 1
+              for (int r = 0; r < D; ++r) add(r, bucket(hp, r, kp));
+              return false;
+            }
 #pragma unroll
-        for (int u = 0; u < kStreamPer; ++u) kk[u] = nx[u];
-        if (base + kStep < hi) fetch(base + kStep);
-#pragma unroll
-        for (int u = 0; u < kStreamPer; ++u) {
-          if (base + tid + (int64_t)u * T >= hi) continue;  // (a raw key may be any 64-bit value)
-          each_bucket<D>(hp, keys.resolve(kk[u]), [&](int r, uint32_t bk) {
-            const uint32_t c = (uint32_t)r * (uint32_t)w + bk;
-            atomicAdd(&lds[c >> 2], 1u << ((c & 3u) << 3));
-          });
-        }
-      }
+            for (int r = 0; r < D; ++r)
+              atomicAdd(reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds) + ((uint32_t)r * (uint32_t)w + (bk[r] & ~3u))),
+                        1u << ((bk[r] << 3) & 31u));
+            return false;
+          },
+          NoRedo{});  // (the redo in place: the kernel has no register left for key_pass' second loop)
       __syncthreads();
       // the image leaves as it is (an owner that overflowed is rewritten whole
       // by mid_rows); each sketch row's sum of squares by v_dot4 of its bytes,
@@ -1798,7 +1877,8 @@ constexpr int kSliceThreads = 512;
 // zeroing, no 64-bit slot atomics; norms from the same pass)
 constexpr bool kWholeSlices = true;
 constexpr int64_t kHotSlice = 65535;  // keys per slice (u16 image, frac_bits 0)
-// D: the depth when it is 4 or 5 (rows unrolled, each_bucket), else 0
+// D: the depth when it is 4 or 5 (rows unrolled: RowHash at a power-of-two
+// width, else each_bucket), else 0
 template <int D>
 __global__ __launch_bounds__(kSliceThreads) void k_build_slices(const int64_t* lo_, const int64_t* hi_, Keys keys,
                                                                 HashParams hp, int64_t slice, const HotInfo* hot,
@@ -1827,37 +1907,74 @@ __global__ __launch_bounds__(kSliceThreads) void k_build_slices(const int64_t* l
   for (int j = (words & ~3) + tid; j < words; j += kSliceThreads) lds[j] = 0u;
   __syncthreads();
   const uint32_t one = 1u << hp.frac_bits;
-  // eight keys per thread per step; the next step's eight loads are issued
-  // before this step's keys are hashed, so a key load's latency is hidden
-  // behind the previous keys' d x 8 hashes and LDS adds
-  constexpr int kPer = 8;  // (4: the same time, profiles/r04/ab_*_s5)
-  constexpr int64_t kStep = kPer * kSliceThreads;
-  uint64_t nx[kPer];
-  auto fetch = [&](int64_t base) {
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-      const int64_t i = base + tid + (int64_t)u * kSliceThreads;
-      nx[u] = i < end ? keys.raw(i) : 0ULL;
-    }
-  };
-  if (lo < end) fetch(lo);
-  for (int64_t base = lo; base < end; base += kStep) {
-    uint64_t kk[kPer];
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) kk[u] = nx[u];
-    if (base + kStep < end) fetch(base + kStep);
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-      if (base + tid + (int64_t)u * kSliceThreads >= end) continue;  // (a raw key may be any 64-bit value)
-      const uint64_t kp = keys.resolve(kk[u]);
-      each_bucket<D>(hp, kp, [&](int r, uint32_t bk) {
-        const uint32_t c = (uint32_t)r * (uint32_t)w + bk;
+  // eight keys per thread per step (4: the same time, profiles/r04/ab_*_s5);
+  // the next step's eight loads are issued before this step's keys are
+  // hashed, so a key load's latency is hidden behind the previous keys' d x 8
+  // hashes and LDS adds
+  constexpr int kPer = 8;
+  auto add = [&](int r, uint32_t bk) {
+    const uint32_t c = (uint32_t)r * (uint32_t)w + bk;
 #ifdef CMS_BUILD_NOLDSADD  // bound analysis only: hashes kept live, no LDS adds
-        if (c == 0xFFFFFFFFu)
+    if (c == 0xFFFFFFFFu)
 #endif
-        atomicAdd(&lds[c >> 1], one << ((c & 1u) << 4));
-      });
+    atomicAdd(&lds[c >> 1], one << ((c & 1u) << 4));
+  };
+  if (kRowHash && D > 0 && hp.fastq) {  // (kernel-uniform)
+    // a key's D rows hashed branch-free into registers (RowHash, cms_hash.h),
+    // one branch per key, then its D adds back to back: the word of counter
+    // (r, bk) is at byte r * 2w | ((bk << 1) & ~3) (w is a power of two) and
+    // the shift of its half takes the low five bits of bk << 4
+    constexpr int DR = D > 0 ? D : 1;
+    RowHash<DR> rh(hp);
+    rh.vgpr();
+    const uint32_t w2 = 2u * (uint32_t)w;
+    auto add_rows = [&](const uint32_t (&bk)[DR]) {
+#pragma unroll
+      for (int r = 0; r < D; ++r) {
+        uint32_t* p = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds) + ((uint32_t)r * w2 | ((bk[r] << 1) & ~3u)));
+#ifdef CMS_BUILD_NOLDSADD
+        if (bk[r] == 0xFFFFFFFFu)
+#endif
+        atomicAdd(p, one << ((bk[r] << 4) & 31u));
+      }
+    };
+    auto redo_key = [&](uint64_t kp) {  // about 1 key in 6,500, and every key that is no u32
+#pragma unroll 1
+      for (int r = 0; r < D; ++r) add(r, bucket(hp, r, kp));
+    };
+    if (keys.tok) {
+      // a token below kTokEscape is the reduced key, a u32 below 2^31; an
+      // escaped one is resolved (from the batch's keys) in the redo
+      const uint32_t* tok = keys.tok;
+      key_pass<uint32_t, kPer, kSliceThreads>(
+          lo, end, tid, [&](int64_t i) { return tok[i]; },
+          [&](uint32_t t) {
+            uint32_t bk[DR];
+            if (rh.rows32(t, bk) || t >= kTokEscape) return true;
+            add_rows(bk);
+            return false;
+          },
+          [&](uint32_t t) { redo_key(keys.resolve(t)); });
+    } else {
+      const int64_t* key = keys.key;
+      key_pass<int64_t, kPer, kSliceThreads>(
+          lo, end, tid, [&](int64_t i) { return key[i]; },
+          [&](int64_t k) {
+            uint32_t bk[DR];
+            if (rh.rows(reduce_key(k), bk)) return true;
+            add_rows(bk);
+            return false;
+          },
+          [&](int64_t k) { redo_key(reduce_key(k)); });
     }
+  } else {
+    key_pass<uint64_t, kPer, kSliceThreads>(
+        lo, end, tid, [&](int64_t i) { return keys.raw(i); },
+        [&](uint64_t raw) {
+          each_bucket<D>(hp, keys.resolve(raw), add);
+          return false;
+        },
+        NoRedo{});
   }
   __syncthreads();
   if (whole && hot[m.x].nslices == 1) {

@@ -200,6 +200,94 @@ CMS_HD void each_bucket(const HashParams& hp, uint64_t kp, F&& f) {
   }
 }
 
+// All D rows of one key without a branch per row (hp.fastq, depth == D): the
+// usual route of bucket_q for every row, the margin tests folded into ONE
+// "redo" answer per key.  The caller hashes a redone key again, row by row,
+// through bucket() -- the exact routes above -- so the buckets it ends with
+// are the BigInteger ones whatever this function wrote for such a key; for a
+// key that is not redone every row passed bucket_q's own condition (floor(y)
+// == q when y's fraction lies in [2^-16, 1 - 2^-16]), and the bucket is
+// bucket_q's: a' k' + b' + 25 q in its low bits.
+//
+// The struct holds what the rows need of a HashParams and nothing else (in a
+// key loop the whole HashParams stayed live and spilled): qa, qb, am = a' &
+// wmask, bm = (uint32_t)b' and the mask.  vgpr() moves qb and bm into vector
+// registers on the device: a gfx9 VOP3 instruction reads one scalar register,
+// so with qa (or am) scalar the other constant of the FMA (the multiply-add)
+// would be copied into a vector register before every hash.
+//
+// redo is returned when
+//   - the key is >= 2^32 - 2.  This covers kp >= 2^32 (not bucket_q's domain)
+//     and every key whose y may reach 2^32: qa, qb <= 1.0, so for k' <= 2^32 -
+//     3 the exact qa k' + qb <= 2^32 - 2, which is a double, and the FMA's one
+//     rounding cannot pass it.  That is the choice made for the q route here:
+//     q is taken by a plain conversion of y (v_cvt_u32_f64, which saturates at
+//     2^32; a C++ cast out of range is undefined), not by bucket_q's 2^52 trick
+//     (two more fp64 instructions a hash), and the two keys from which y can
+//     reach 2^32 go to the redo instead, where bucket_q's 33-bit q0 decides;
+//   - a row's fraction lies outside the margin, tested on the fraction's high
+//     dword: hi in [0x3EF00000, 0x3FEFFFDF] implies 2^-16 <= fr < 1 - 2^-16
+//     (the upper bound gives away the last 2^-36 below 1 - 2^-16; a denormal
+//     or zero fraction has a small high dword and fails the lower bound).
+// The fraction is y - floor(y) on the host and v_fract_f64 on the device (the
+// same value for 0 <= y < 2^32: the subtraction is exact and below 1).  Were
+// a redo decision ever to differ between host and device, the buckets still
+// could not: either side's answer is exact.
+constexpr uint32_t kFracHiMin = 0x3EF00000u;  // high dword of 2^-16
+constexpr uint32_t kFracHiMax = 0x3FEFFFDFu;  // the last high dword below 1 - 2^-16's (0x3FEFFFE0)
+constexpr uint64_t kRowHashKeyEnd = 0xFFFFFFFEULL;  // keys from here on are redone
+template <int D>
+struct RowHash {
+  double qa[D], qb[D];
+  uint32_t am[D], bm[D];
+  uint32_t wmask;
+  CMS_HD explicit RowHash(const HashParams& hp) : wmask(hp.wmask) {
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      qa[r] = hp.qa[r];
+      qb[r] = hp.qb[r];
+      am[r] = (uint32_t)hp.ap[r] & hp.wmask;
+      bm[r] = (uint32_t)hp.bp[r];
+    }
+  }
+  CMS_HD void vgpr() {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      asm volatile("" : "+v"(qb[r]));
+      asm volatile("" : "+v"(bm[r]));
+    }
+#endif
+  }
+  // a key below 2^32 - 2 (the caller's word for it: a token is below 2^31)
+  CMS_HD bool rows32(uint32_t k, uint32_t (&bk)[D]) const {
+    const double kf = (double)k;
+    const uint32_t km = k & wmask;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      const double y = fma(qa[r], kf, qb[r]);
+#if defined(__HIP_DEVICE_COMPILE__)
+      const double fr = __builtin_amdgcn_fract(y);
+      const uint32_t q = (uint32_t)y;
+#else
+      const double fr = y - floor(y);
+      const uint32_t q = (uint32_t)(int64_t)y;  // (defined for the redone keys too: y <= 2^32 + 1)
+#endif
+      const uint32_t fh = (uint32_t)(__builtin_bit_cast(uint64_t, fr) >> 32);
+      lo = fh < lo ? fh : lo;
+      hi = fh > hi ? fh : hi;
+      bk[r] = (CMS_MUL24(am[r], km) + bm[r] + CMS_MUL24(q, 25u)) & wmask;
+    }
+    return lo < kFracHiMin || hi > kFracHiMax;
+  }
+  // any reduced key
+  CMS_HD bool rows(uint64_t kp, uint32_t (&bk)[D]) const {
+    const bool far = kp >= kRowHashKeyEnd;
+    return rows32((uint32_t)kp, bk) || far;
+  }
+};
+
 // Bucket for an arbitrary width w with its Barrett constant floor((2^64-1)/w)
 // (per-owner sketch shapes: CosineCM hashes u1 at u2's width).
 CMS_HD uint32_t bucket_wb(const HashParams& hp, int r, uint64_t kp, uint32_t w, uint64_t barrett) {
