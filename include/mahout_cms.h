@@ -487,6 +487,25 @@ int cms_load_table(cms_handle* h, const char* path);
  * still set).  Blocking: the image is complete when the call returns. */
 int cms_save_table_device(cms_handle* h, void* d_buf, int64_t capacity, int64_t* bytes);
 int cms_load_table_device(cms_handle* h, const void* d_buf, int64_t bytes);
+/* Merging: a count-min sketch is linear, so an image adds counter by counter
+ * into a live table built with the same hash functions: table[r][i][j] +=
+ * image[r][i][j], row_mass[r] += the image's, pairs_ingested += the image's.
+ * The handle is fixed-shape and without a communicator (CMS_E_STATE otherwise),
+ * empty or populated, before or after cms_finalize; afterwards it is
+ * "ingested, not finalized", exactly as after a COO batch (cms_finalize
+ * re-derives the norms; kept cms_top_k_refresh lists stay, the image's
+ * non-empty rows marked touched).  Depth, width, num_owners, counter type and
+ * frac_bits, the hash parameters in use (a_i, b_i for i < depth, drawn or
+ * installed) and the owner-ID sections (both absent, or identical) must equal
+ * the image's: CMS_E_PARAM.  u32 counters: no row's mass + image mass may reach
+ * 2^32 (CMS_E_OVERFLOW).  A pending device-ingest error is reported first, as
+ * cms_synchronize would.  Every check -- header, directory, payload checksum,
+ * pad bytes and every list row's entries, over the WHOLE image -- precedes
+ * every write: a refused merge leaves the live table bit for bit as it was.
+ * The file is staged whole in device memory first (CMS_E_OOM when it does not
+ * fit beside the table). */
+int cms_merge_table(cms_handle* h, const char* path);
+int cms_merge_table_device(cms_handle* h, const void* d_buf, int64_t bytes);
 /* The parameters a handle needs to load the file (host only: no device call):
  * depth, width, counter type, seed, num_owners and frac_bits from its header;
  * weighting unweighted, device -1, flags 0.  CMS_E_PARAM for a file that is

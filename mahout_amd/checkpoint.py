@@ -171,6 +171,37 @@ def read_checkpoint(path):
         return Checkpoint(f.read())
 
 
+def sum_counters(paths_or_checkpoints):
+    """The counters [n][d][w] (as Checkpoint.counters()) of the images' streams
+    together: the no-GPU specification of SketchTable.merge.  A count-min
+    sketch is linear, so tables built with the same hash functions add counter
+    by counter.  The images must agree in shape, counter type, frac_bits, the
+    hash parameters in use (a_i, b_i for i < depth) and their owner IDs (all
+    absent, or all identical), and -- u32 counters -- no row's summed mass may
+    reach 2^32: ValueError otherwise, as the library refuses the merge."""
+    cks = [c if isinstance(c, Checkpoint) else read_checkpoint(c) for c in paths_or_checkpoints]
+    if not cks:
+        raise ValueError("no checkpoint to sum")
+    first = cks[0]
+    total = first.counters()
+    mass = first.masses.copy()
+    for c in cks[1:]:
+        for f in ("depth", "width", "num_owners", "counter_type", "frac_bits"):
+            if getattr(c, f) != getattr(first, f):
+                raise ValueError("checkpoints differ in %s" % f)
+        if not (np.array_equal(c.a, first.a) and np.array_equal(c.b, first.b)):
+            raise ValueError("checkpoints were built with different hash parameters")
+        if (c.owner_ids is None) != (first.owner_ids is None) or (
+                c.owner_ids is not None and not np.array_equal(c.owner_ids, first.owner_ids)):
+            raise ValueError("checkpoints differ in their owner IDs")
+        if first.counter_type == 0:
+            if np.any(mass >= 2 ** 32) or np.any(c.masses >= 2 ** 32) or np.any(mass + c.masses >= 2 ** 32):
+                raise ValueError("a row's total increment reached 2^32 (u32 counters)")
+        mass = mass + c.masses
+        total = total + c.counters()
+    return total
+
+
 if __name__ == "__main__":
     import sys
     c = read_checkpoint(sys.argv[1])

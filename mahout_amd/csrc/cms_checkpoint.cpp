@@ -141,5 +141,53 @@ const char* check_directory(const Header& hd, const DirEntry* dir, int64_t n) {
   return nullptr;
 }
 
+// ---- cms_merge_table: every check here, like those above, precedes every
+// write -- and the table it protects is populated, so a refusal must leave it
+// bit for bit as it was ----
+
+const char* check_merge_params(const Header& hd, const int64_t* live_a, const int64_t* live_b, const int64_t* live_ids,
+                               const int64_t* image_ids) {
+  // a sum of sketches under different hash functions is silently wrong
+  for (int i = 0; i < hd.depth; ++i)
+    if (hd.a[i] != live_a[i] || hd.b[i] != live_b[i]) return "the image was built with other hash parameters";
+  if ((live_ids == nullptr) != (image_ids == nullptr))
+    return live_ids ? "the handle has owner IDs, the image has none" : "the image has owner IDs, the handle has none";
+  if (live_ids && std::memcmp(live_ids, image_ids, 8 * (size_t)hd.num_owners) != 0)
+    return "the image's owner IDs differ from the handle's";
+  return nullptr;
+}
+
+const char* check_merge_masses(const Header& hd, const DirEntry* dir, const uint64_t* live_mass, int64_t n) {
+  if (hd.counter_type != 0) return nullptr;
+  for (int64_t r = 0; r < n; ++r) {
+    const uint64_t m = live_mass ? live_mass[r] : 0;
+    // (either term alone past 2^32 also refuses: the sum below cannot wrap then)
+    if (m >= (uint64_t(1) << 32) || dir[r].mass >= (uint64_t(1) << 32) || m + dir[r].mass >= (uint64_t(1) << 32))
+      return "a row's total increment reached 2^32 (u32 counters)";
+  }
+  return nullptr;
+}
+
+uint64_t merge_increment(const DirEntry& e) {
+  if (e.len == 0) return 0;
+  uint64_t cap;
+  switch (e.form) {
+    case kRowList:
+      if (e.len <= 2) return 0;  // (no entries)
+      cap = 255;                 // a list row's counters are below 2^8
+      break;
+    case kRowU1: cap = 1; break;
+    case kRowU2: cap = 3; break;
+    case kRowU4: cap = 15; break;
+    case kRowU8: cap = 255; break;
+    // a u16 row in a whole slot takes its adds without a cbound update
+    // (k_widen_mark skips it), so only its form and its mass bound it
+    case kRowU16: return e.mass < 65535 ? e.mass : 65535;
+    default: return e.mass;  // hot, fp64
+  }
+  if (e.cbound != 0 && e.cbound < cap) cap = e.cbound;
+  return e.mass < cap ? e.mass : cap;
+}
+
 }  // namespace ckpt
 }  // namespace cms

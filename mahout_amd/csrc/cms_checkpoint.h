@@ -89,5 +89,20 @@ const char* check_directory(const Header& hd, const DirEntry* dir, int64_t n);
 // stored bytes of a dense form's row (0: zero rows, lists and unknown forms)
 uint64_t dense_len(int form, int64_t dw);
 
+// ---- merging an image into a live table (cms_merge_table) ----
+// The image adds counter by counter only under the live table's hash
+// functions and owner universe: a[i], b[i] for i < depth must equal the
+// header's (rows >= depth are not in use), and the ID sections must agree --
+// both absent (null), or both present and identical.  nullptr: compatible.
+const char* check_merge_params(const Header& hd, const int64_t* live_a, const int64_t* live_b, const int64_t* live_ids,
+                               const int64_t* image_ids);
+// u32 counters: a row's mass plus the image's reaches 2^32 (the ingest's rule:
+// old + inc >= 2^32).  nullptr: every row fits (always for fp64 counters).
+const char* check_merge_masses(const Header& hd, const DirEntry* dir, const uint64_t* live_mass, int64_t n);
+// the most the image's row can add to one counter of the live row: min(cbound,
+// mass) for a form row (a list's counters are bounded the same way), the mass
+// for a hot or fp64 row, 0 for a row that stores nothing
+uint64_t merge_increment(const DirEntry& e);
+
 }  // namespace ckpt
 }  // namespace cms

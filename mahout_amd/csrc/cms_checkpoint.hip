@@ -21,6 +21,15 @@
 //   k_ckpt_expand  a handle without forms (CMS_NO_FORMS=1) receives narrow
 //                  rows expanded to u16
 //
+// cms_merge_table adds an image into a live table (a count-min sketch is
+// linear).  Every check precedes every write: k_ckpt_unpack<false> verifies
+// the whole resident image without a store, then the in-place writers'
+// promote / widen step prepares the live rows, then
+//
+//   k_ckpt_add        dense image rows of any form into dense live rows of
+//                     any form, on the unpack's source-driven tile mapping
+//   k_ckpt_add_lists  list image rows, one workgroup per row, counted in LDS
+//
 // The payload offsets are summed on the host from the directory's read-back
 // (64-bit: 16-byte units of a 79 GB arena pass 2^32); the same read-back
 // sizes the image.
@@ -44,7 +53,7 @@ using namespace ckpt;
 constexpr int kTileChunks = 1024;        // 16-byte chunks per workgroup tile (16 KB)
 constexpr uint64_t kListBit = 1ull << 63;  // seg_len: the segment is a list row (validated by the unpack)
 constexpr uint64_t kIoChunk = 64ull << 20;  // bytes per pinned staging buffer of the file path
-enum : unsigned long long { kBadList = 1, kBadPad = 2 };
+enum : unsigned long long { kBadList = 1, kBadPad = 2, kBadDest = 4 };
 
 // The rows that have stored bytes, in row order: payload byte offsets
 // (off[nseg] = the payload's length), device addresses and lengths.
@@ -202,7 +211,9 @@ __global__ __launch_bounds__(256) void k_ckpt_pack(SegView sv, uint64_t c0, uint
 // what was read, out[1] |= kBad*.  A list row's chunk is checked before it is
 // stored: its leading u16 must be the key count its length implies and every
 // entry a bucket (< width) -- the readers index LDS by these entries.  A chunk
-// that fails is not stored.
+// that fails is not stored.  kStore = false is the merge's verify pass: the
+// same mapping, checksum and checks over an image, and no store at all.
+template <bool kStore>
 __global__ __launch_bounds__(256) void k_ckpt_unpack(SegView sv, uint64_t c0, uint64_t c1, const uint8_t* src, int depth,
                                                      int width, unsigned long long* out) {
   __shared__ uint64_t s_off[kTileChunks + 1];
@@ -248,7 +259,7 @@ __global__ __launch_bounds__(256) void k_ckpt_unpack(SegView sv, uint64_t c0, ui
           }
         }
       }
-      if (ok) store16(reinterpret_cast<uint8_t*>(sv.addr[s]) + rel, rem, v);
+      if (kStore && ok) store16(reinterpret_cast<uint8_t*>(sv.addr[s]) + rel, rem, v);
     }
     __syncthreads();
   }
@@ -280,6 +291,248 @@ __global__ __launch_bounds__(256) void k_ckpt_expand(const int32_t* rows, const 
         unpack16(f, p8, j, v);
         pack16<2>(v, dst, j);
       }
+    }
+  }
+}
+
+// ---- merge: the image's rows added into the live rows (cms_merge_table) ----
+//
+// The source's form is independent of the destination's: promote_rows and
+// widen_rows ran first on the rows' bounds, so every live row that receives
+// anything is dense -- a 1-bit ... u16 row in a place that holds it, or a u32
+// hot slot -- and no field of it carries.  A group of N source counters
+// (N = 16, or 8 from a u16 chunk and from the list re-count) lands on N tb / 8
+// whole bytes of the destination, aligned to their own size, that no other
+// lane touches: a plain load, add, store.
+
+struct AddDst {
+  uint8_t* p;  // the live row's first byte
+  int tb;      // bits per counter: a narrow form's 1 .. 16, 32 for a hot slot; 0: the row takes no adds
+};
+__device__ __forceinline__ AddDst add_dst(const TableView& tv, int64_t r) {
+  const int32_t s = tv.hidx[r];
+  if (s >= 0) return AddDst{reinterpret_cast<uint8_t*>(tv.hot + (int64_t)s * tv.dw), 32};
+  const int64_t o = tv.off[r];
+  if (s == kFormList || o == 0) return AddDst{nullptr, 0};  // (widen_rows rewrote these: never the shared zero row)
+  return AddDst{reinterpret_cast<uint8_t*>(tv.t16 + (o & ~kCapMask)), form_bits(s)};
+}
+
+// counters [j, j + N) of the TB-bit row at p += v
+template <int TB, int N>
+__device__ __forceinline__ void add_fields(uint8_t* p, int64_t j, const uint32_t (&v)[N]) {
+  constexpr int kBits = TB * N;
+  uint8_t* q = p + ((j * TB) >> 3);
+  if constexpr (kBits >= 32) {
+    constexpr int kWords = kBits / 32, kPer = 32 / TB;
+    uint32_t inc[kWords];
+#pragma unroll
+    for (int k = 0; k < kWords; ++k) {
+      inc[k] = 0;
+#pragma unroll
+      for (int c = 0; c < kPer; ++c) inc[k] |= v[k * kPer + c] << (c * TB);
+    }
+    if constexpr (kWords % 4 == 0) {
+#pragma unroll
+      for (int k = 0; k < kWords; k += 4) {
+        uint4* d = reinterpret_cast<uint4*>(q) + k / 4;
+        uint4 x = *d;
+        x.x += inc[k], x.y += inc[k + 1], x.z += inc[k + 2], x.w += inc[k + 3];
+        *d = x;
+      }
+    } else if constexpr (kWords == 2) {
+      uint2* d = reinterpret_cast<uint2*>(q);
+      uint2 x = *d;
+      x.x += inc[0], x.y += inc[1];
+      *d = x;
+    } else {
+      *reinterpret_cast<uint32_t*>(q) += inc[0];
+    }
+  } else {
+    uint32_t inc = 0;
+#pragma unroll
+    for (int c = 0; c < N; ++c) inc |= v[c] << (c * TB);
+    if constexpr (kBits == 16) *reinterpret_cast<uint16_t*>(q) += (uint16_t)inc;
+    else *q += (uint8_t)inc;
+  }
+}
+
+// counters [j, j + cnt) of the live row += v[0 .. cnt) (j % N == 0; v past cnt
+// is zero: a narrow row's last partial group adds nothing to the slack of its
+// own slot, a hot row -- whose neighbour follows at once -- stops at cnt)
+template <int N>
+__device__ __forceinline__ void add_hot(uint32_t* d, const uint32_t (&v)[N], int cnt) {
+  if (cnt == N && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
+#pragma unroll
+    for (int k = 0; k < N; k += 4) {
+      uint4 x = reinterpret_cast<uint4*>(d)[k / 4];
+      x.x += v[k], x.y += v[k + 1], x.z += v[k + 2], x.w += v[k + 3];
+      reinterpret_cast<uint4*>(d)[k / 4] = x;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+      if (k < cnt) d[k] += v[k];
+  }
+}
+template <int N>
+__device__ __forceinline__ void add_counters(const AddDst& dst, int64_t j, const uint32_t (&v)[N], int cnt) {
+  switch (dst.tb) {
+    case 32: add_hot<N>(reinterpret_cast<uint32_t*>(dst.p) + j, v, cnt); break;
+    case 16: add_fields<16, N>(dst.p, j, v); break;
+    case 8: add_fields<8, N>(dst.p, j, v); break;
+    case 4: add_fields<4, N>(dst.p, j, v); break;
+    case 2: add_fields<2, N>(dst.p, j, v); break;
+    case 1: add_fields<1, N>(dst.p, j, v); break;
+    default: break;
+  }
+}
+
+// counters [16 g, 16 g + 16) of a 16-byte chunk w of SB-bit counters; false: all zero
+template <int SB>
+__device__ __forceinline__ bool chunk_counters(const uint32_t (&w)[4], int g, uint32_t (&v)[16]) {
+  uint32_t any = 0;
+  if constexpr (SB == 8) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) v[q] = (w[q >> 2] >> ((q & 3) * 8)) & 255u;
+    any = w[0] | w[1] | w[2] | w[3];
+  } else if constexpr (SB == 4) {
+    const uint32_t a = g ? w[2] : w[0], b = g ? w[3] : w[1];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) v[q] = ((q < 8 ? a : b) >> ((q & 7) * 4)) & 15u;
+    any = a | b;
+  } else {
+    const int i = SB == 2 ? g : g >> 1;
+    uint32_t x = i == 0 ? w[0] : i == 1 ? w[1] : i == 2 ? w[2] : w[3];
+    if constexpr (SB == 1) x = (x >> ((g & 1) * 16)) & 0xFFFFu;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) v[q] = (x >> (q * SB)) & ((1u << SB) - 1u);
+    any = x;
+  }
+  return any != 0;
+}
+
+// Dense image rows (1-bit ... u16, u32 hot, fp64) of the resident payload src
+// added into the live table: k_ckpt_unpack's source-driven mapping, where
+// sv.addr[s] is the segment's owner row and a list segment is left to
+// k_ckpt_add_lists.  A lane takes one 16-byte chunk: 128 / sb counters of one
+// row.  t64: the fp64 table (then every segment is an fp64 row).  out[1] |=
+// kBadDest when a live row is in no state to take adds (the driver's
+// promote / widen step makes that impossible).
+__global__ __launch_bounds__(256) void k_ckpt_add(SegView sv, uint64_t c1, const uint8_t* src, TableView tv, double* t64,
+                                                  unsigned long long* out) {
+  __shared__ uint64_t s_off[kTileChunks + 1];
+  unsigned long long bad = 0;
+  const int64_t dw = tv.dw;
+  const uint64_t tiles = (c1 + kTileChunks - 1) / kTileChunks;
+  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const uint64_t t0 = t * kTileChunks, t1 = min<uint64_t>(t0 + (uint64_t)kTileChunks, c1);
+    int64_t first;
+    int cnt;
+    tile_setup(sv, t0, s_off, first, cnt);
+    for (uint64_t c = t0 + threadIdx.x; c < t1; c += 256) {
+      const uint64_t pos = c * 16;
+      const int i = tile_find(s_off, cnt, pos);
+      const int64_t s = first + i;
+      const uint64_t rel = pos - s_off[i];
+      const uint64_t len = sv.len[s];
+      if ((len & kListBit) || rel >= len) continue;
+      const int64_t r = (int64_t)sv.addr[s];
+      const int rem = (int)min<uint64_t>(len - rel, 16);
+      const uint4 x = *reinterpret_cast<const uint4*>(src + pos);
+      const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+      if (t64) {  // one correctly rounded add per counter (always done: x + 0.0 is not x for every x)
+        double* d = t64 + r * dw + (int64_t)(rel >> 3);
+        d[0] += __longlong_as_double((long long)((uint64_t)w[0] | ((uint64_t)w[1] << 32)));
+        if (rem == 16) d[1] += __longlong_as_double((long long)((uint64_t)w[2] | ((uint64_t)w[3] << 32)));
+        continue;
+      }
+      if ((w[0] | w[1] | w[2] | w[3]) == 0) continue;  // (most chunks of a sparse 1- or 2-bit row)
+      const AddDst dst = add_dst(tv, r);
+      const int sb = (int)((len * 8) / (uint64_t)dw);
+      if (dst.tb == 0 || (sb == 32 && dst.tb != 32)) {
+        bad |= kBadDest;
+        continue;
+      }
+      uint32_t v[16];
+      switch (sb) {
+        case 32: {  // u32 -> u32
+          const uint32_t v4[4] = {w[0], w[1], w[2], w[3]};
+          add_hot<4>(reinterpret_cast<uint32_t*>(dst.p) + (int64_t)(rel >> 2), v4, rem >> 2);
+          break;
+        }
+        case 16: {
+          uint32_t v8[8];
+#pragma unroll
+          for (int q = 0; q < 8; ++q) v8[q] = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
+          add_counters<8>(dst, (int64_t)(rel >> 1), v8, rem >> 1);
+          break;
+        }
+        case 8:
+          chunk_counters<8>(w, 0, v);
+          add_counters<16>(dst, (int64_t)rel, v, 16);
+          break;
+        case 4:
+#pragma unroll 1
+          for (int g = 0; g < 2; ++g)
+            if (chunk_counters<4>(w, g, v)) add_counters<16>(dst, (int64_t)rel * 2 + 16 * g, v, 16);
+          break;
+        case 2:
+#pragma unroll 1
+          for (int g = 0; g < 4; ++g)
+            if (chunk_counters<2>(w, g, v)) add_counters<16>(dst, (int64_t)rel * 4 + 16 * g, v, 16);
+          break;
+        case 1:
+#pragma unroll 1
+          for (int g = 0; g < 8; ++g)
+            if (chunk_counters<1>(w, g, v)) add_counters<16>(dst, (int64_t)rel * 8 + 16 * g, v, 16);
+          break;
+        default: bad |= kBadDest; break;
+      }
+    }
+    __syncthreads();
+  }
+  if (bad) atomicOr(out + 1, bad);
+}
+
+// List image rows: one workgroup per listed row (rows[i], its payload offset
+// off[i] and key count m[i] from the validated directory).  A list's entries
+// scatter, so each sketch row is counted in LDS first (u8 counters, four per
+// word, as k_widen_rows' re-count: a list row's counters are below 2^8), then
+// every lane adds groups of 8 counters -- at least one whole byte of the
+// narrowest form -- skipping the groups that counted nothing.  The workgroup
+// owns the live row: no global atomics.  The verify pass checked every entry;
+// the bound test below only keeps LDS safe should the caller's device image
+// change under the call.
+__global__ __launch_bounds__(256) void k_ckpt_add_lists(const int32_t* rows, const uint64_t* off, const uint32_t* lm,
+                                                        int64_t count, const uint8_t* src, TableView tv, int depth,
+                                                        unsigned long long* out) {
+  extern __shared__ uint32_t lc[];  // [w / 4]
+  const int w = tv.w;
+  for (int64_t i = blockIdx.x; i < count; i += gridDim.x) {
+    const int64_t r = rows[i];
+    const uint16_t* e = reinterpret_cast<const uint16_t*>(src + off[i]) + 1;
+    const uint32_t m = lm[i];
+    const AddDst dst = add_dst(tv, r);
+    if (dst.tb == 0) {  // (uniform over the workgroup)
+      if (threadIdx.x == 0) atomicOr(out + 1, (unsigned long long)kBadDest);
+      continue;
+    }
+    for (int rr = 0; rr < depth; ++rr) {
+      for (int j = threadIdx.x; j < (w >> 2); j += 256) lc[j] = 0u;
+      __syncthreads();
+      for (uint32_t t = threadIdx.x; t < m; t += 256) {
+        const uint32_t b = e[(uint32_t)rr * m + t];
+        if (b < (uint32_t)w) atomicAdd(&lc[b >> 2], 1u << ((b & 3u) * 8u));
+      }
+      __syncthreads();
+      for (int q = threadIdx.x; q < (w >> 3); q += 256) {
+        const uint32_t lo = lc[2 * q], hi = lc[2 * q + 1];
+        if ((lo | hi) == 0) continue;
+        const uint32_t v[8] = {lo & 255u, (lo >> 8) & 255u, (lo >> 16) & 255u, lo >> 24,
+                               hi & 255u, (hi >> 8) & 255u, (hi >> 16) & 255u, hi >> 24};
+        add_counters<8>(dst, (int64_t)rr * w + 8 * q, v, 8);
+      }
+      __syncthreads();  // the counts are added before the next sketch row zeroes them
     }
   }
 }
@@ -421,7 +674,7 @@ int unpack_range(cms_handle* h, const Segs& sg, uint64_t c0, uint64_t c1, const 
                  unsigned long long* d_out) {
   if (c1 <= c0) return CMS_OK;
   TimedScope ts(h, "ckpt_unpack");
-  hipLaunchKernelGGL(k_ckpt_unpack, dim3(grid_for(h, c1 - c0)), dim3(256), 0, h->stream, sg.view(), c0, c1, d_src,
+  hipLaunchKernelGGL(k_ckpt_unpack<true>, dim3(grid_for(h, c1 - c0)), dim3(256), 0, h->stream, sg.view(), c0, c1, d_src,
                      (int)h->p.depth, (int)h->p.width, d_out);
   CMS_HIP(hipGetLastError());
   return CMS_OK;
@@ -432,10 +685,10 @@ struct Staging {
   void* pin[2] = {nullptr, nullptr};
   DevBuf dev[2];
   hipEvent_t ev_a[2] = {nullptr, nullptr}, ev_b[2] = {nullptr, nullptr};
-  int init(uint64_t bytes) {
+  int init(uint64_t bytes, bool with_dev = true) {  // (the merge copies straight into its resident image)
     for (int i = 0; i < 2; ++i) {
       CMS_HIP(hipHostMalloc(&pin[i], (size_t)bytes, hipHostMallocDefault));
-      CMS_HIP(dev[i].ensure((size_t)bytes));
+      if (with_dev) CMS_HIP(dev[i].ensure((size_t)bytes));
       CMS_HIP(hipEventCreateWithFlags(&ev_a[i], hipEventDisableTiming));
       CMS_HIP(hipEventCreateWithFlags(&ev_b[i], hipEventDisableTiming));
     }
@@ -564,11 +817,17 @@ int save_device(cms_handle* h, void* d_buf, int64_t capacity, int64_t* bytes) {
 
 // ---- load ----
 
-int check_loadable(cms_handle* h, const char* what) {
+// what a load and a merge both need: one fixed-shape table that no rank shares
+int check_receives_image(cms_handle* h, const char* what) {
   if (h->per_owner)
     return set_error(CMS_E_STATE, "%s: a per-owner-shape handle keeps the DataModel, not a table", what);
   if (h->comm || h->ext_comm || h->multi())
     return set_error(CMS_E_STATE, "%s: the handle has a communicator (the merge would sum every rank's copy)", what);
+  return CMS_OK;
+}
+
+int check_loadable(cms_handle* h, const char* what) {
+  if (int rc = check_receives_image(h, what)) return rc;
   if (!h->empty || h->pairs_ingested != 0)
     return set_error(CMS_E_STATE, "%s: the handle must be empty (new, or after cms_reset)", what);
   return CMS_OK;
@@ -893,6 +1152,205 @@ int load_device(cms_handle* h, const void* d_buf, int64_t bytes) {
   return commit_load(h, im, ex, res);
 }
 
+// ---- merge ----
+
+// The image (head parsed and validated into im, payload resident at d_payload,
+// 16-byte aligned) added into the live table.  Every check -- the header-level
+// compatibility, the overflow rule, then the verify pass over the whole
+// payload -- precedes the first write: a refusal leaves the table as it was.
+int merge_resident(cms_handle* h, Image& im, const uint8_t* d_payload) {
+  const Header& hd = im.hd;
+  const int64_t n = h->n;
+  if (const char* why = check_merge_params(hd, h->a, h->b, h->h_owner_ids.empty() ? nullptr : h->h_owner_ids.data(),
+                                           im.ids.empty() ? nullptr : im.ids.data()))
+    return set_error(CMS_E_PARAM, "checkpoint: %s", why);
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  std::vector<uint64_t> mass((size_t)n, 0);  // the live masses, then the merged ones
+  if (!h->empty) CMS_HIP(hipMemcpy(mass.data(), h->d_row_mass, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost));
+  if (const char* why = check_merge_masses(hd, im.dir.data(), mass.data(), n)) return set_error(CMS_E_OVERFLOW, "%s", why);
+
+  // the verify pass: checksum, pad bytes and every list row over the resident bytes, no store
+  Segs sg;
+  im.addr.resize((size_t)n);
+  for (int64_t r = 0; r < n; ++r) im.addr[r] = (uint64_t)r;  // (k_ckpt_add: a segment's owner row)
+  build_segs(im, sg);
+  int rc = sg.upload(h);
+  if (rc) return rc;
+  DevBuf d_out;
+  unsigned long long res[2] = {0, 0};
+  const uint64_t chunks = hd.payload_bytes / 16;
+  CMS_HIP(d_out.ensure(2 * sizeof(unsigned long long)));
+  CMS_HIP(hipMemsetAsync(d_out.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
+  if (chunks > 0) {
+    TimedScope ts(h, "ckpt_verify");
+    hipLaunchKernelGGL(k_ckpt_unpack<false>, dim3(grid_for(h, chunks)), dim3(256), 0, h->stream, sg.view(), (uint64_t)0,
+                       chunks, d_payload, (int)h->p.depth, (int)h->p.width, d_out.as<unsigned long long>());
+    CMS_HIP(hipGetLastError());
+  }
+  CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  if (res[1] & kBadList) return set_error(CMS_E_PARAM, "checkpoint: a list row's key count or an entry is out of range");
+  if (res[1] & kBadPad) return set_error(CMS_E_PARAM, "checkpoint: padding bytes are not zero");
+  if (res[0] != hd.checksum) return set_error(CMS_E_PARAM, "checkpoint: payload checksum mismatch");
+
+  // ---- every check has passed: the first write follows ----
+  std::vector<int32_t> lrow;  // the image's list rows that hold entries
+  std::vector<uint64_t> loff;
+  std::vector<uint32_t> lm;
+  std::vector<int64_t> touched;  // rows the image adds to (the refresh marks them)
+  std::vector<uint64_t> bound;   // (host arrays of the uploads below live until the last synchronisation)
+  std::vector<uint8_t> force;
+  DevBuf d_lrow, d_loff, d_lm, d_touched;
+  if (h->f64) {
+    if (h->empty) {
+      CMS_HIP(hipMemsetAsync(h->d_t64, 0, sizeof(double) * (size_t)n * (size_t)h->dw, h->stream));
+      CMS_HIP(hipMemsetAsync(h->d_row_mass, 0, sizeof(uint64_t) * (size_t)n, h->stream));
+    }
+    for (int64_t r = 0; r < n; ++r)
+      if (im.dir[r].len) touched.push_back(r);
+  } else {
+    // the in-place writers' sequence (ingest_coo_device): per-row bounds, promote, widen
+    bound.assign((size_t)n, 0);
+    force.assign((size_t)n, 0);
+    for (int64_t r = 0; r < n; ++r) {
+      const DirEntry& e = im.dir[r];
+      const uint64_t inc = merge_increment(e);
+      if (inc == 0) continue;  // (nothing stored, or every stored counter is zero: mass 0)
+      bound[r] = mass[r] + inc;
+      force[r] = e.form == kRowHot;  // a live row that receives u32 counters holds u32 counters
+      touched.push_back(r);
+      if (e.form == kRowList) {
+        lrow.push_back((int32_t)r);
+        loff.push_back(e.off);
+        lm.push_back((uint32_t)((e.len - 2) / (2 * (uint64_t)hd.depth)));
+      }
+    }
+    // rows that add nothing leave the segments: their live rows were not prepared for an add
+    for (size_t s = 0, r = 0; s < sg.len.size(); ++s) {
+      while (im.dir[r].len == 0) ++r;
+      if (bound[r] == 0) sg.len[s] |= kListBit;  // (k_ckpt_add skips list segments)
+      ++r;
+    }
+    if ((rc = sg.upload(h))) return rc;
+    if (h->empty) {  // as a COO batch into an empty table
+      if ((rc = reset_rows_zero(h))) return rc;
+      CMS_HIP(hipMemsetAsync(h->d_row_mass, 0, sizeof(uint64_t) * (size_t)n, h->stream));
+      h->norms_valid = false;
+    }
+    CMS_HIP(h->ws_bound.ensure(sizeof(uint64_t) * (size_t)n));
+    CMS_HIP(h->ws_force.ensure((size_t)n));
+    CMS_HIP(hipMemcpyAsync(h->ws_bound.ptr, bound.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    CMS_HIP(hipMemcpyAsync(h->ws_force.ptr, force.data(), (size_t)n, hipMemcpyHostToDevice, h->stream));
+    if ((rc = promote_rows(h, h->ws_bound.as<uint64_t>(), h->ws_force.as<uint8_t>(), true))) return rc;
+    if ((rc = widen_rows(h, h->ws_bound.as<uint64_t>(), h->d_row_mass, false))) return rc;
+  }
+  if (h->rf_valid && !touched.empty()) {  // cms_top_k_refresh stays incremental after a delta merge
+    CMS_HIP(d_touched.ensure(sizeof(int64_t) * touched.size()));
+    CMS_HIP(hipMemcpyAsync(d_touched.ptr, touched.data(), sizeof(int64_t) * touched.size(), hipMemcpyHostToDevice, h->stream));
+    if ((rc = refresh_mark(h, d_touched.as<int64_t>(), (int64_t)touched.size()))) return rc;
+  }
+  if (!lrow.empty()) {
+    const size_t k = lrow.size();
+    CMS_HIP(d_lrow.ensure(sizeof(int32_t) * k));
+    CMS_HIP(d_loff.ensure(sizeof(uint64_t) * k));
+    CMS_HIP(d_lm.ensure(sizeof(uint32_t) * k));
+    CMS_HIP(hipMemcpyAsync(d_lrow.ptr, lrow.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, h->stream));
+    CMS_HIP(hipMemcpyAsync(d_loff.ptr, loff.data(), sizeof(uint64_t) * k, hipMemcpyHostToDevice, h->stream));
+    CMS_HIP(hipMemcpyAsync(d_lm.ptr, lm.data(), sizeof(uint32_t) * k, hipMemcpyHostToDevice, h->stream));
+  }
+  {
+    TimedScope ts(h, "ckpt_add");
+    if (chunks > 0)
+      hipLaunchKernelGGL(k_ckpt_add, dim3(grid_for(h, chunks)), dim3(256), 0, h->stream, sg.view(), chunks, d_payload,
+                         h->tview(), h->f64 ? h->d_t64 : (double*)nullptr, d_out.as<unsigned long long>());
+    if (!lrow.empty())
+      hipLaunchKernelGGL(k_ckpt_add_lists, dim3((unsigned)std::min<size_t>(lrow.size(), 65536)), dim3(256),
+                         (size_t)h->p.width, h->stream, d_lrow.as<int32_t>(), d_loff.as<uint64_t>(), d_lm.as<uint32_t>(),
+                         (int64_t)lrow.size(), d_payload, h->tview(), (int)h->p.depth, d_out.as<unsigned long long>());
+    CMS_HIP(hipGetLastError());
+  }
+  for (int64_t r = 0; r < n; ++r) mass[r] += im.dir[r].mass;  // the true masses, not the bounds
+  CMS_HIP(hipMemcpyAsync(h->d_row_mass, mass.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  // "ingested, not finalized", as after a COO batch; cms_finalize re-derives norms and row maxima
+  h->pairs_ingested += hd.pairs_ingested;
+  h->empty = false;
+  h->norms_valid = false;
+  h->finalized = false;
+  h->stale_possible = true;
+  if (res[1] & kBadDest) return set_error(CMS_E_STATE, "cms_merge_table: a live row was in no form to take its adds");
+  return CMS_OK;
+}
+
+// The file is staged whole in device memory (through two pinned buffers), then
+// merged as a device image: the verify pass must see all of it before the
+// first write, and a list row may straddle any staging boundary.
+int merge_file(cms_handle* h, const char* path) {
+  File in;
+  in.f = std::fopen(path, "rb");
+  if (!in.f) return set_error(CMS_E_PARAM, "cannot open %s", path);
+  Image im;
+  if (std::fseek(in.f, 0, SEEK_END) != 0) return set_error(CMS_E_PARAM, "cannot seek in %s", path);
+  const long long size = (long long)std::ftell(in.f);
+  std::rewind(in.f);
+  if (size < (long long)sizeof(Header) || std::fread(&im.hd, sizeof(Header), 1, in.f) != 1)
+    return set_error(CMS_E_PARAM, "checkpoint %s: shorter than a checkpoint header", path);
+  if (const char* why = check_header(im.hd, (uint64_t)size)) return set_error(CMS_E_PARAM, "checkpoint %s: %s", path, why);
+  int rc = check_matches(h, im.hd);
+  if (rc) return rc;
+  const Header& hd = im.hd;
+  {
+    std::vector<uint8_t> head((size_t)hd.payload_off);
+    std::rewind(in.f);
+    if (std::fread(head.data(), 1, head.size(), in.f) != head.size())
+      return set_error(CMS_E_PARAM, "checkpoint %s: short read", path);
+    if ((rc = parse_head(head.data(), im))) return rc;
+  }
+  DevBuf payload;
+  if (payload.ensure((size_t)std::max<uint64_t>(hd.payload_bytes, 16)) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_error(CMS_E_OOM, "cms_merge_table: no device memory to stage the %.2f GB image", 1e-9 * (double)hd.payload_bytes);
+  }
+  const uint64_t nchunks = (hd.payload_bytes + kIoChunk - 1) / kIoChunk;
+  if (nchunks > 0) {
+    Staging st;
+    if ((rc = st.init(std::min(kIoChunk, hd.payload_bytes), false))) return rc;
+    const auto t_io = std::chrono::steady_clock::now();
+    for (uint64_t i = 0; i < nchunks; ++i) {
+      const int b = (int)(i & 1);
+      const uint64_t o = i * kIoChunk, len = std::min(kIoChunk, hd.payload_bytes - o);
+      if (i >= 2) CMS_HIP(hipEventSynchronize(st.ev_a[b]));  // pin[b] has left the host
+      if (std::fread(st.pin[b], 1, (size_t)len, in.f) != len) return set_error(CMS_E_PARAM, "checkpoint %s: short read", path);
+      CMS_HIP(hipMemcpyAsync(payload.as<uint8_t>() + o, st.pin[b], (size_t)len, hipMemcpyHostToDevice, h->side_stream));
+      CMS_HIP(hipEventRecord(st.ev_a[b], h->side_stream));
+    }
+    CMS_HIP(hipStreamSynchronize(h->side_stream));
+    add_host_time(h, "ckpt_io", t_io);
+  }
+  return merge_resident(h, im, payload.as<uint8_t>());
+}
+
+int merge_device(cms_handle* h, const void* d_buf, int64_t bytes) {
+  if (bytes < (int64_t)sizeof(Header)) return set_error(CMS_E_PARAM, "checkpoint image: shorter than a checkpoint header");
+  if (reinterpret_cast<uintptr_t>(d_buf) & 15) return set_error(CMS_E_PARAM, "device image must be 16-byte aligned");
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  Image im;
+  CMS_HIP(hipMemcpy(&im.hd, d_buf, sizeof(Header), hipMemcpyDeviceToHost));
+  if (const char* why = check_header(im.hd, (uint64_t)bytes)) return set_error(CMS_E_PARAM, "checkpoint image: %s", why);
+  int rc = check_matches(h, im.hd);
+  if (rc) return rc;
+  const Header& hd = im.hd;
+  {
+    std::vector<uint8_t> head((size_t)hd.payload_off);
+    CMS_HIP(hipMemcpy(head.data(), d_buf, head.size(), hipMemcpyDeviceToHost));
+    if (std::memcmp(head.data(), &im.hd, sizeof(Header)) != 0)
+      return set_error(CMS_E_PARAM, "checkpoint image changed while it was read");
+    if ((rc = parse_head(head.data(), im))) return rc;
+  }
+  return merge_resident(h, im, static_cast<const uint8_t*>(d_buf) + hd.payload_off);
+}
+
 }  // namespace
 }  // namespace cms
 
@@ -934,6 +1392,22 @@ int cms_load_table_device(cms_handle* h, const void* d_buf, int64_t bytes) {
   if (!h || !d_buf) return set_error(CMS_E_PARAM, "null argument");
   Guard g(h);
   return load_device(h, d_buf, bytes);
+}
+
+int cms_merge_table(cms_handle* h, const char* path) {
+  if (!h || !path) return set_error(CMS_E_PARAM, "null argument");
+  if (int rc = cms_synchronize(h)) return rc;  // a pending device-ingest error comes first: nothing is merged
+  Guard g(h);
+  if (int rc = check_receives_image(h, "cms_merge_table")) return rc;
+  return merge_file(h, path);
+}
+
+int cms_merge_table_device(cms_handle* h, const void* d_buf, int64_t bytes) {
+  if (!h || !d_buf) return set_error(CMS_E_PARAM, "null argument");
+  if (int rc = cms_synchronize(h)) return rc;
+  Guard g(h);
+  if (int rc = check_receives_image(h, "cms_merge_table_device")) return rc;
+  return merge_device(h, d_buf, bytes);
 }
 
 int cms_checkpoint_info(const char* path, cms_params* out, int64_t* file_bytes) {

@@ -562,6 +562,23 @@ class SketchTable:
         torch.cuda.current_stream(image.device).synchronize()  # its producers are done
         check(self._lib.cms_load_table_device(self._h, ctypes.c_void_p(image.data_ptr()), int(image.numel())))
 
+    def merge(self, path):
+        """A checkpoint file added into this table, counter by counter
+        (cms_merge_table): the table of both streams together.  The handle may
+        be empty or populated; shape, counter type, hash parameters and owner
+        IDs must equal the file's.  A refused merge changes nothing;
+        finalize() afterwards re-derives the norms."""
+        check(self._lib.cms_merge_table(self._h, os.fsencode(path)))
+
+    def merge_device(self, image):
+        """merge() of a checkpoint image (uint8 tensor on the handle's device,
+        as save_device() returns it; cms_merge_table_device)."""
+        import torch
+        if image.device != torch.device("cuda", self.device) or image.dtype != torch.uint8 or not image.is_contiguous():
+            raise ValueError("image must be a contiguous uint8 tensor on cuda:%d" % self.device)
+        torch.cuda.current_stream(image.device).synchronize()  # its producers are done
+        check(self._lib.cms_merge_table_device(self._h, ctypes.c_void_p(image.data_ptr()), int(image.numel())))
+
     @classmethod
     def from_checkpoint(cls, path, device=-1, weighted=False):
         """A new handle of the file's shape (cms_checkpoint_info), loaded from it."""
