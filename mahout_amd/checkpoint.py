@@ -1,8 +1,10 @@
-"""read_checkpoint: a pure-numpy reader of the checkpoint image (format
-version 1, DESIGN.md 3 "Checkpoint image") -- no GPU and no library.
+"""read_checkpoint / write_checkpoint: a pure-numpy reader and writer of the
+checkpoint image (format version 1, DESIGN.md 3 "Checkpoint image") -- no GPU
+and no library.
 
 The format's independent second implementation (the tests decode what the GPU
-wrote with it) and an inspection tool:
+wrote with the reader, and load tables designed counter by counter through the
+writer: build_checkpoint) and an inspection tool:
 
     python -m mahout_amd.checkpoint table.ckpt
 
@@ -161,6 +163,16 @@ class Checkpoint:
             out = np.ldexp(out, -self.frac_bits)
         return out
 
+    def list_entries(self, r):
+        """The stored entries [d][m] (u16 buckets, in stored order) of list row r."""
+        if ROW_FORMS[int(self.forms[r])] != "list":
+            raise ValueError("row %d is not a list row" % r)
+        e = self.row_bytes(r).view("<u2")
+        m = int(e[0])
+        if e.size != 1 + self.depth * m:
+            raise ValueError("row %d: list key count disagrees with its length" % r)
+        return e[1:].reshape(self.depth, m).copy()
+
     def form_counts(self):
         return {ROW_FORMS[f]: int(c) for f, c in enumerate(np.bincount(self.forms, minlength=len(ROW_FORMS))) if c}
 
@@ -169,6 +181,255 @@ def read_checkpoint(path):
     """Decode a checkpoint file (ValueError when it is not a valid image)."""
     with open(path, "rb") as f:
         return Checkpoint(f.read())
+
+
+# ---- the writer ----
+
+_FORM = {name: i for i, name in enumerate(ROW_FORMS)}
+_NARROW = ("u1", "u2", "u4", "u8", "u16")           # place classes 1..5
+LIST_MAX_KEYS, LIST_MAX_ENTRIES = 1024, 8192        # the longest list a build stores (kListMaxKeys/Entries)
+MAX_DEPTH, MAX_OWNERS = 32, 1 << 24
+
+
+def shape_has_form(name, depth, width):
+    """Whether a u32 table of this shape stores rows of this form: 1-bit rows
+    need w % 128 == 0, 2-bit rows w % 64 == 0, any narrow form and lists
+    w % 32 == 0, lists a u16 row of at most 80 KiB as well."""
+    forms = width % 32 == 0
+    if name == "u1":
+        return forms and width % 128 == 0
+    if name == "u2":
+        return forms and width % 64 == 0
+    if name in ("u4", "u8"):
+        return forms
+    if name == "list":
+        return forms and 2 * depth * width <= 80 * 1024
+    return name in ("zero", "u16", "u32")
+
+
+def default_form(cmax, mass, depth, width):
+    """The form (a ROW_FORMS name) a row with largest counter cmax and mass
+    `mass` is stored in: u32 from 2^16 on, else the narrowest dense form that
+    holds cmax among those the shape has."""
+    if mass >= 1 << 16 or cmax >= 1 << 16:
+        return "u32"
+    for name in _NARROW:
+        if cmax < 1 << _BITS[name] and shape_has_form(name, depth, width):
+            return name
+    return "u16"
+
+
+def _pack_dense(c, name):
+    """Rows [k][d*w] (uint64) of one dense form -> their stored bytes [k][len]."""
+    bits = _BITS[name]
+    if bits >= 8:
+        return np.ascontiguousarray(c.astype("<u%d" % (bits // 8))).view(np.uint8).reshape(c.shape[0], -1)
+    per = 8 // bits  # counter j in bits (j % per) * bits of byte j // per
+    v = c.astype(np.uint8).reshape(c.shape[0], -1, per)
+    sh = (np.arange(per, dtype=np.uint8) * bits)[None, None, :]
+    return np.bitwise_or.reduce(v << sh, axis=2).astype(np.uint8)
+
+
+def build_checkpoint(counters, a, b, *, seed=0, frac_bits=0, owner_ids=None, forms=None, classes=None, bounds=None,
+                     masses=None, lists=None, pairs_ingested=None):
+    """The checkpoint image (bytes) of a designed table: the format's writer.
+
+    counters: [n][d][w] unsigned integers in counter units (a u32 table), or a
+    float64 array (an fp64 table: every row form f64).  a, b: the hash
+    parameters in use, at least d each.  The per-row arguments are sequences
+    of n entries, or None for the defaults, which are what a saving handle
+    writes:
+
+      forms    ROW_FORMS names or indices; None or -1 for a row: u32 when the
+               row's mass or a counter reaches 2^16, else the narrowest dense
+               form the shape has that holds the largest counter (an all-zero
+               row is a dense row of zeros; form "zero" only when asked for)
+      classes  place classes; default the form's own (u1..u16 = 1..5), 0 for
+               list, zero, u32 and f64 rows
+      bounds   cbound; default the row's largest counter, 0 for u32/f64 rows
+      masses   default the owner's largest row sum (0 in an fp64 table)
+      lists    {row: entries [d][m]} or a sequence with None: the row is
+               stored as that list, which must count to counters[row]
+      pairs_ingested  default the sum of the masses
+
+    ValueError for what the loader would refuse: a counter above its form's
+    capacity, a form the shape lacks, a place class narrower than the form, a
+    list past the stored limits or with an entry outside the row, a mass of
+    2^32 or more (u32 counters), owner IDs that do not strictly ascend."""
+    counters = np.asarray(counters)
+    if counters.ndim != 3:
+        raise ValueError("counters must be [n][d][w]")
+    n, d, w = counters.shape
+    f64 = counters.dtype.kind == "f"
+    if not f64 and counters.dtype.kind not in "ui":
+        raise ValueError("counters must be unsigned integers or float64")
+    if not f64 and counters.dtype.kind == "i" and counters.size and int(counters.min()) < 0:
+        raise ValueError("negative counter")
+    if not 1 <= d <= MAX_DEPTH or not 1 <= w <= (1 << 20 if f64 else 1 << 15) or not 1 <= n <= MAX_OWNERS:
+        raise ValueError("shape outside what a handle holds")
+    if not 0 <= frac_bits <= 31:
+        raise ValueError("frac_bits outside [0, 31]")
+    a, b = np.asarray(a, np.int64), np.asarray(b, np.int64)
+    if a.size < d or b.size < d or a.size > 32 or b.size > 32:
+        raise ValueError("one (a, b) per sketch row")
+    if owner_ids is not None:
+        owner_ids = np.asarray(owner_ids, np.int64)
+        if owner_ids.shape != (n,) or np.any(np.diff(owner_ids) <= 0):
+            raise ValueError("owner IDs must be n strictly ascending values")
+    dw = d * w
+    flat = counters.reshape(n, dw)
+    if f64:
+        flat = flat.astype(np.float64)
+        cmax = np.zeros(n, np.uint64)
+        mass_def = np.zeros(n, np.uint64)
+    else:
+        flat = flat.astype(np.uint64)
+        if flat.size and int(flat.max()) >= 1 << 32:
+            raise ValueError("a counter of 2^32 or more")
+        cmax = flat.max(axis=1)
+        mass_def = counters.astype(np.uint64).sum(axis=2).max(axis=1)
+    mass = mass_def if masses is None else np.asarray(masses, np.uint64)
+    if mass.shape != (n,):
+        raise ValueError("one mass per owner")
+    if not f64 and np.any(mass >= np.uint64(1 << 32)):
+        raise ValueError("a row mass of 2^32 or more (u32 counters)")
+    if isinstance(lists, dict):
+        lists = [lists.get(r) for r in range(n)]
+    if lists is not None and len(lists) != n:
+        raise ValueError("one list (or None) per owner")
+
+    # -- forms --
+    form = np.full(n, -1, np.int32)
+    if forms is not None:
+        if len(forms) != n:
+            raise ValueError("one form per owner")
+        for r, f in enumerate(forms):
+            if f is None:
+                continue
+            f = _FORM.get(f, f) if isinstance(f, str) else int(f)
+            if not isinstance(f, int) or not -1 <= f < len(ROW_FORMS):
+                raise ValueError("row %d: unknown row form" % r)
+            form[r] = f
+    if lists is not None:
+        for r, ent in enumerate(lists):
+            if ent is None:
+                continue
+            if form[r] not in (-1, _FORM["list"]):
+                raise ValueError("row %d: list entries for a row of another form" % r)
+            form[r] = _FORM["list"]
+    todo = np.flatnonzero(form < 0)
+    if f64:
+        form[todo] = _FORM["f64"]
+    elif todo.size:
+        # (vectorised default_form)
+        pick = np.full(todo.size, _FORM["u16"], np.int32)
+        for name in reversed(_NARROW[:-1]):
+            if shape_has_form(name, d, w):
+                pick[cmax[todo] < np.uint64(1 << _BITS[name])] = _FORM[name]
+        pick[(mass[todo] >= np.uint64(1 << 16)) | (cmax[todo] >= np.uint64(1 << 16))] = _FORM["u32"]
+        form[todo] = pick
+
+    # -- every check the loader makes, and the counters against their forms --
+    need_cls = np.zeros(n, np.int32)
+    length = np.zeros(n, np.int64)
+    list_raw = {}
+    for fi, name in enumerate(ROW_FORMS):
+        rows = np.flatnonzero(form == fi)
+        if rows.size == 0:
+            continue
+        if f64 != (name == "f64") and name != "zero":
+            raise ValueError("row %d: a %s row in %s table" % (rows[0], name, "an fp64" if f64 else "a u32"))
+        if not f64 and not shape_has_form(name, d, w):
+            raise ValueError("row %d: a %s row in a shape that has none" % (rows[0], name))
+        if name == "zero":
+            if np.any(flat[rows] != 0):
+                raise ValueError("a zero row with counters")
+        elif name == "list":
+            for r in rows.tolist():
+                ent = None if lists is None else lists[r]
+                if ent is None:
+                    raise ValueError("row %d: a list row needs its entries" % r)
+                ent = np.asarray(ent)
+                if ent.ndim != 2 or ent.shape[0] != d:
+                    raise ValueError("row %d: list entries must be [d][m]" % r)
+                m = ent.shape[1]
+                ln = 2 + 2 * d * m
+                if m > LIST_MAX_KEYS or m * d > LIST_MAX_ENTRIES or ln > 2 * dw:
+                    raise ValueError("row %d: list row too long" % r)
+                if m and (int(ent.min()) < 0 or int(ent.max()) >= w):
+                    raise ValueError("row %d: list entry outside the sketch row" % r)
+                cnt = np.stack([np.bincount(ent[i].astype(np.int64), minlength=w) for i in range(d)]) if m else 0
+                if np.any(flat[r].reshape(d, w) != cnt):
+                    raise ValueError("row %d: the list does not count to the row's counters" % r)
+                list_raw[r] = np.concatenate([[m], ent.reshape(-1)]).astype("<u2").view(np.uint8)
+                length[r] = ln
+        else:
+            if name in _NARROW:
+                need_cls[rows] = 1 + _NARROW.index(name)
+            if not f64 and _BITS[name] < 64 and np.any(cmax[rows] >= np.uint64(1) << np.uint64(_BITS[name])):
+                bad = rows[cmax[rows] >= np.uint64(1) << np.uint64(_BITS[name])][0]
+                raise ValueError("row %d: a counter above the capacity of form %s" % (bad, name))
+            length[rows] = dw * _BITS[name] // 8
+    cls = need_cls.copy() if classes is None else np.asarray(classes, np.int32)
+    if cls.shape != (n,) or np.any(cls < need_cls) or np.any(cls > 5):
+        raise ValueError("a place class narrower than the row's form, or unknown")
+    no_place = np.isin(form, [_FORM["zero"], _FORM["u32"], _FORM["f64"]])
+    if np.any(cls[no_place] != 0):
+        raise ValueError("zero, u32 and f64 rows have no arena place")
+    if bounds is None:
+        cb = np.where(no_place & (form != _FORM["zero"]), 0, cmax).astype(np.uint64)
+    else:
+        cb = np.asarray(bounds, np.uint64)
+    if cb.shape != (n,) or np.any(cb >= np.uint64(1 << 32)):
+        raise ValueError("one u32 cbound per owner")
+
+    # -- layout and payload --
+    padded = (length + 15) // 16 * 16
+    off = np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.int64)
+    payload = np.zeros(int(padded.sum()), np.uint8)
+    for fi, name in enumerate(ROW_FORMS):
+        rows = np.flatnonzero(form == fi)
+        if rows.size == 0 or name in ("zero", "list"):
+            continue
+        raw = (np.ascontiguousarray(flat[rows].astype("<f8")).view(np.uint8).reshape(rows.size, -1) if name == "f64"
+               else _pack_dense(flat[rows], name))
+        payload[off[rows][:, None] + np.arange(raw.shape[1])[None, :]] = raw
+    for r, raw in list_raw.items():
+        payload[off[r]:off[r] + raw.size] = raw
+    payload = payload.tobytes()
+
+    dire = np.zeros(n, DIR_ENTRY)
+    dire["form"], dire["cls"], dire["cbound"] = form, cls, cb
+    dire["len"], dire["mass"], dire["off"] = length, mass, off
+    hd = np.zeros(1, HEADER)
+    h = hd[0]
+    ids_off, ids_bytes, dir_off, dir_bytes, payload_off = section_layout(n, owner_ids is not None)
+    h["magic"], h["version"], h["header_bytes"] = MAGIC, VERSION, HEADER_BYTES
+    h["depth"], h["width"], h["counter_type"], h["frac_bits"] = d, w, int(f64), frac_bits
+    h["num_owners"], h["seed"] = n, seed
+    h["pairs_ingested"] = int(mass.sum(dtype=np.uint64)) if pairs_ingested is None else int(pairs_ingested)
+    if int(h["pairs_ingested"]) < 0:
+        raise ValueError("negative pairs_ingested")
+    h["flags"], h["dir_entry_bytes"] = (FLAG_OWNER_IDS if owner_ids is not None else 0), DIR_ENTRY.itemsize
+    h["ids_off"], h["ids_bytes"], h["dir_off"], h["dir_bytes"] = ids_off, ids_bytes, dir_off, dir_bytes
+    h["payload_off"], h["payload_bytes"] = payload_off, len(payload)
+    h["checksum"] = payload_checksum(payload)
+    h["file_bytes"] = payload_off + len(payload)
+    h["a"][:d], h["b"][:d] = a[:d], b[:d]
+    out = bytearray(hd.tobytes())
+    if owner_ids is not None:
+        out += owner_ids.astype("<i8").tobytes()
+    out += bytes(dir_off - len(out)) + dire.tobytes() + payload
+    assert len(out) == int(h["file_bytes"])
+    return bytes(out)
+
+
+def write_checkpoint(path, counters, a, b, **kw):
+    """build_checkpoint(...) written to `path`; returns the byte count."""
+    data = build_checkpoint(counters, a, b, **kw)
+    with open(path, "wb") as f:
+        f.write(data)
+    return len(data)
 
 
 def sum_counters(paths_or_checkpoints):

@@ -1398,7 +1398,11 @@ int cms_top_k_all_device(cms_handle* h, int32_t k, int64_t* d_ids, double* d_sco
 static int top_k_refresh_job(cms_handle* h, int32_t k, int64_t* o_ids, double* o_sc, int32_t* o_cnt) {
   const int64_t n = h->n;
   int rc = CMS_OK;
-  if (h->per_owner || h->f64)  // no kept lists for these modes: the whole job
+  // no kept lists for these modes: the whole job.  A width without limb images
+  // (mfma_eligible) takes the per-row path, which never lays the owners out:
+  // cosine_prepare has not run, so h_inv and the class counts the incremental
+  // path reads below do not exist.
+  if (h->per_owner || h->f64 || !mfma_eligible(h))
     return top_k_all_job(h, k, o_ids, o_sc, o_cnt);
   // kept lists are twice as deep as the answer, so a few candidates of an
   // untouched owner may leave before its list must be recomputed

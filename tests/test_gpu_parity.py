@@ -576,8 +576,8 @@ def test_top_k_heavy_ties(oracle):
     (2000, 4, 128, 50, 100, False, 52),   # most owners multi-limb: several S x M passes
     (1800, 3, 256, 1, 64, True, 53),      # weighted: every score is +-1, ties by ID everywhere
     (700, 5, 512, 2, 5, False, 54),       # fewer than one 256-row block pair per wave
-    (11776, 3, 128, 2, 20, False, 55),    # 46 blocks: multi-wave bands and the half wave
-    (12000, 4, 256, 2, 25, False, 56),    # fp4 blocks beside int8 blocks over multi-wave bands
+    (11776, 3, 128, 2, 20, False, 55),    # 16 blocks of 768 rows: every band one wave, and the half wave
+    (12000, 4, 256, 2, 25, False, 56),    # fp4 blocks beside int8 blocks (16 blocks: single-wave bands)
     (5000, 2, 512, 1, 200, False, 57),    # mostly fp4 owners, long lists
     (3000, 5, 8192, 3, 100, False, 58),   # the config-4 shape (d=5, w=8192): fp4, int8 and multi-limb owners
 ])

@@ -67,7 +67,7 @@ def _batch(rng, n, frac, size, vmax, n_keys):
 
 
 @pytest.mark.parametrize("n,d,w,vmax,k,weighted,seed", [
-    (12000, 4, 256, 2, 25, False, 56),    # fp4 blocks beside int8 blocks, multi-wave bands
+    (12000, 4, 256, 2, 25, False, 56),    # fp4 blocks beside int8 blocks: 16 blocks of 768 rows, every band one wave
     (11776, 3, 128, 2, 20, False, 55),    # no fp4 image (w % 256): int8 waves only
     (3000, 5, 8192, 3, 100, False, 58),   # the config-4 shape: fp4, int8 and multi-limb owners
     (1800, 3, 256, 1, 64, True, 53),      # weighted: not on the symmetric kernel (all pairs recomputed)
@@ -117,6 +117,32 @@ def test_refresh_equals_whole_job(n, d, w, vmax, k, weighted, seed, oracle):
         again = t.top_k_refresh(k)
         assert t.refresh_stats()[0] == 0
         assert _same_lists(again, exp) is None
+
+
+@pytest.mark.parametrize("w", [64, 96])
+def test_refresh_at_a_width_without_limb_images(oracle, w):
+    """w % 128 != 0: the all-pairs job takes the per-row path and never lays the
+    owners out (no cosine_prepare, so no h_inv).  The incremental refresh used
+    to index that empty vector for every touched owner and crashed the
+    process; such a handle now refreshes by the whole job."""
+    n, d, k = 600, 2, 10
+    items, users = zipf_stream(2000, n, 40_000, seed=91)
+    rows = np.array([0, 3, 17, n - 1], np.int64)
+    keys = np.array([5, 6, 7, 8], np.int64)
+    a, b = oracle.hash_params(42, d)
+    with SketchTable(n, depth=d, width=w, seed=42) as t:
+        t.ingest(items, users)
+        t.finalize()
+        err = _same_lists(t.top_k_refresh(k), t.top_k_all(k))
+        assert err is None, err
+        t.ingest(rows, keys)
+        t.finalize()
+        got = t.top_k_refresh(k)
+        err = _same_lists(got, t.top_k_all(k))
+        assert err is None, err
+        table = oracle.build_table(n, d, w, a, b, np.concatenate([items, rows]), np.concatenate([users, keys]))
+        err = _oracle_rows(oracle, table, got, [0, 1, 3, 17, 300, n - 1], k)
+        assert err is None, err
 
 
 def test_refresh_owner_ids_and_invalidation():
