@@ -47,7 +47,7 @@ extern "C" {
 #define CMS_E_NO_SUCH_ID 3 /* NoSuchUserException / NoSuchItemException (GenericDataModel.java:210-215) */
 #define CMS_E_STATE 4      /* call-order violation (query before finalize, ...) */
 #define CMS_E_VALUE 5      /* increment not a non-negative multiple of 2^-frac_bits below 2^(32-frac_bits) */
-#define CMS_E_OVERFLOW 6   /* a counter could exceed the counter type */
+#define CMS_E_OVERFLOW 6   /* a counter could exceed the counter type or fall below zero */
 #define CMS_E_HIP 7        /* HIP runtime error */
 #define CMS_E_RCCL 8       /* RCCL error */
 #define CMS_E_OOM 9        /* device or host allocation failed */
@@ -506,6 +506,28 @@ int cms_load_table_device(cms_handle* h, const void* d_buf, int64_t bytes);
  * fit beside the table). */
 int cms_merge_table(cms_handle* h, const char* path);
 int cms_merge_table_device(cms_handle* h, const void* d_buf, int64_t bytes);
+/* Subtracting: the other half of the merge.  If the image was built with the
+ * same hash functions and its stream is a sub-stream of the live table's,
+ * table - image is, counter for counter, the table of the remaining stream
+ * (merge today's delta, subtract the delta from N days ago: a sliding window).
+ * table[r][i][j] -= image[r][i][j], row_mass[r] -= the image's,
+ * pairs_ingested -= the image's (saturating at 0: instrumentation only).
+ * Accepted under the merge's rules, in the merge's order, and: u32 counters
+ * only -- an fp64 handle returns CMS_E_STATE, since (a + b) - b is not a in
+ * fp64 and the result would be no stream's table; no row mass may fall below
+ * zero (live mass >= image mass for every row, so an empty handle accepts
+ * only an image whose masses are all 0) and no single counter may fall below
+ * zero (live >= image for every (r, i, j); a device pass over the whole image
+ * against the live rows in whatever form they are in): CMS_E_OVERFLOW, the
+ * message naming an offending owner row.  Every check precedes every write: a
+ * refused subtraction leaves every counter, place, form, bound, mass and
+ * pairs_ingested bit for bit as they were.  Afterwards the handle is
+ * "ingested, not finalized" as after a merge; the rows the image subtracts
+ * from are marked for cms_top_k_refresh.  Dense live rows keep form and place
+ * (nothing narrows, demotes or returns to the shared zero row); a live list
+ * row that loses entries is rewritten densely first. */
+int cms_subtract_table(cms_handle* h, const char* path);
+int cms_subtract_table_device(cms_handle* h, const void* d_buf, int64_t bytes);
 /* The parameters a handle needs to load the file (host only: no device call):
  * depth, width, counter type, seed, num_owners and frac_bits from its header;
  * weighting unweighted, device -1, flags 0.  CMS_E_PARAM for a file that is

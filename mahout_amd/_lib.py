@@ -46,7 +46,7 @@ EXPORTS = [
     "cms_comm_init_transport", "cms_read_counters_device", "cms_owner_forms", "cms_estimate_preferences_batch", "cms_top_k_refresh", "cms_refresh_stats", "cms_refresh_classes",
     "cms_top_k_all_device", "cms_top_k_refresh_device", "cms_set_hash_params", "cms_recommend_batch",
     "cms_checkpoint_size", "cms_save_table", "cms_load_table", "cms_save_table_device", "cms_load_table_device",
-    "cms_checkpoint_info", "cms_merge_table", "cms_merge_table_device",
+    "cms_checkpoint_info", "cms_merge_table", "cms_merge_table_device", "cms_subtract_table", "cms_subtract_table_device",
 ]
 
 
@@ -174,6 +174,8 @@ _SIGS = {
     "cms_load_table_device": (_int, [_vp, _vp, _i64]),
     "cms_merge_table": (_int, [_vp, ctypes.c_char_p]),
     "cms_merge_table_device": (_int, [_vp, _vp, _i64]),
+    "cms_subtract_table": (_int, [_vp, ctypes.c_char_p]),
+    "cms_subtract_table_device": (_int, [_vp, _vp, _i64]),
     "cms_checkpoint_info": (_int, [ctypes.c_char_p, ctypes.POINTER(CmsParams), ctypes.POINTER(_i64)]),
 }
 

@@ -463,6 +463,39 @@ def sum_counters(paths_or_checkpoints):
     return total
 
 
+def diff_counters(minuend, subtrahend):
+    """(counters [n][d][w] as Checkpoint.counters(), masses [n] uint64) of the
+    minuend's stream without the subtrahend's: the no-GPU specification of
+    SketchTable.subtract and the counterpart of sum_counters.  Both are paths
+    or Checkpoint objects.  ValueError, as the library refuses the call, when
+    the images differ in shape, counter type, frac_bits, the hash parameters in
+    use or their owner IDs, when either holds fp64 counters ((a + b) - b is
+    not a there), and when a row's mass or any single counter would fall below
+    zero."""
+    a, b = (c if isinstance(c, Checkpoint) else read_checkpoint(c) for c in (minuend, subtrahend))
+    for f in ("depth", "width", "num_owners", "counter_type", "frac_bits"):
+        if getattr(a, f) != getattr(b, f):
+            raise ValueError("checkpoints differ in %s" % f)
+    if a.counter_type != 0:
+        raise ValueError("fp64 counters do not subtract")
+    if not (np.array_equal(a.a, b.a) and np.array_equal(a.b, b.b)):
+        raise ValueError("checkpoints were built with different hash parameters")
+    if (a.owner_ids is None) != (b.owner_ids is None) or (
+            a.owner_ids is not None and not np.array_equal(a.owner_ids, b.owner_ids)):
+        raise ValueError("checkpoints differ in their owner IDs")
+    if np.any(a.masses < b.masses):
+        raise ValueError("row %d: the mass would fall below zero" % int(np.flatnonzero(a.masses < b.masses)[0]))
+    out = np.zeros((a.num_owners, a.depth, a.width), np.float64)
+    for r in range(a.num_owners):
+        x, y = a.row_counters(r), b.row_counters(r)  # uint64, counter units
+        if np.any(x < y):
+            raise ValueError("row %d: a counter would fall below zero" % r)
+        out[r] = x - y
+    if a.frac_bits:
+        out = np.ldexp(out, -a.frac_bits)
+    return out, a.masses - b.masses
+
+
 if __name__ == "__main__":
     import sys
     c = read_checkpoint(sys.argv[1])

@@ -168,6 +168,15 @@ const char* check_merge_masses(const Header& hd, const DirEntry* dir, const uint
   return nullptr;
 }
 
+const char* check_subtract_masses(const Header& hd, const DirEntry* dir, const uint64_t* live_mass, int64_t n) {
+  if (hd.counter_type != 0) return "fp64 counters do not subtract";
+  for (int64_t r = 0; r < n; ++r) {
+    const uint64_t m = live_mass ? live_mass[r] : 0;
+    if (m < dir[r].mass) return "a row's mass would fall below zero: the image is no part of this table's stream";
+  }
+  return nullptr;
+}
+
 uint64_t merge_increment(const DirEntry& e) {
   if (e.len == 0) return 0;
   uint64_t cap;

@@ -104,5 +104,14 @@ const char* check_merge_masses(const Header& hd, const DirEntry* dir, const uint
 // for a hot or fp64 row, 0 for a row that stores nothing
 uint64_t merge_increment(const DirEntry& e);
 
+// ---- subtracting an image from a live table (cms_subtract_table) ----
+// u32 counters only.  No row's mass may fall below zero: live_mass[r] >=
+// dir[r].mass for every r (live_mass null: an empty table, mass 0 everywhere,
+// which accepts only an image whose masses are all 0).  The comparison is
+// made on the 64-bit masses as they are: nothing is added, nothing wraps.
+// nullptr: every row's mass stays at or above zero.  (The masses cannot show a
+// single counter going below zero: that is the device's check.)
+const char* check_subtract_masses(const Header& hd, const DirEntry* dir, const uint64_t* live_mass, int64_t n);
+
 }  // namespace ckpt
 }  // namespace cms

@@ -30,6 +30,17 @@
 //                     any form, on the unpack's source-driven tile mapping
 //   k_ckpt_add_lists  list image rows, one workgroup per row, counted in LDS
 //
+// cms_subtract_table is the other half: image B's stream being a sub-stream of
+// the live table's, table - B is the table of the remaining stream.  After the
+// same verify pass a second pass compares every image counter with its live
+// counter, in whatever form either row is in, and stores nothing; only then
+// are live list rows rewritten densely (widen_rows) and the image subtracted:
+//
+//   k_ckpt_sub<false / true>       dense image rows against dense live rows,
+//                                  on k_ckpt_add's mapping: compare, or subtract
+//   k_ckpt_sub_rows<false / true>  rows where either side is a list, one
+//                                  workgroup per row, counted in LDS
+//
 // The payload offsets are summed on the host from the directory's read-back
 // (64-bit: 16-byte units of a 79 GB arena pass 2^32); the same read-back
 // sizes the image.
@@ -53,7 +64,7 @@ using namespace ckpt;
 constexpr int kTileChunks = 1024;        // 16-byte chunks per workgroup tile (16 KB)
 constexpr uint64_t kListBit = 1ull << 63;  // seg_len: the segment is a list row (validated by the unpack)
 constexpr uint64_t kIoChunk = 64ull << 20;  // bytes per pinned staging buffer of the file path
-enum : unsigned long long { kBadList = 1, kBadPad = 2, kBadDest = 4 };
+enum : unsigned long long { kBadList = 1, kBadPad = 2, kBadDest = 4, kBadUnder = 8 };
 
 // The rows that have stored bytes, in row order: payload byte offsets
 // (off[nseg] = the payload's length), device addresses and lengths.
@@ -533,6 +544,328 @@ __global__ __launch_bounds__(256) void k_ckpt_add_lists(const int32_t* rows, con
         add_counters<8>(dst, (int64_t)rr * w + 8 * q, v, 8);
       }
       __syncthreads();  // the counts are added before the next sketch row zeroes them
+    }
+  }
+}
+
+// ---- subtract: the image's rows compared with, then taken out of, the live rows (cms_subtract_table) ----
+//
+// The addressing is the add's: a group of N source counters faces N tb / 8
+// whole bytes of the live row that no other lane touches.  kWrite = false is
+// the check -- the group is loaded and compared field by field, true when any
+// live field is below its image counter, and nothing is stored.  kWrite =
+// true follows a check that passed for the whole image: every decrement fits
+// its field, so the packed word of decrements subtracts with one integer
+// subtract and no borrow crosses a field.  The one group below a byte -- four
+// u32 image counters on a 1-bit live row, half a byte that the next lane's
+// chunk shares -- subtracts with an atomic on the aligned word.
+
+template <int TB, int N, bool kWrite>
+__device__ __forceinline__ bool sub_fields(uint8_t* p, int64_t j, const uint32_t (&v)[N]) {
+  constexpr int kBits = TB * N;
+  constexpr uint32_t kMask = (1u << TB) - 1u;
+  uint8_t* q = p + ((j * TB) >> 3);
+  bool under = false;
+  if constexpr (kBits >= 32) {
+    constexpr int kWords = kBits / 32, kPer = 32 / TB;
+    uint32_t x[kWords];
+    if constexpr (kWords % 4 == 0) {
+#pragma unroll
+      for (int k = 0; k < kWords; k += 4) {
+        const uint4 y = reinterpret_cast<const uint4*>(q)[k / 4];
+        x[k] = y.x, x[k + 1] = y.y, x[k + 2] = y.z, x[k + 3] = y.w;
+      }
+    } else if constexpr (kWords == 2) {
+      const uint2 y = *reinterpret_cast<const uint2*>(q);
+      x[0] = y.x, x[1] = y.y;
+    } else {
+      x[0] = *reinterpret_cast<const uint32_t*>(q);
+    }
+    if constexpr (kWrite) {
+#pragma unroll
+      for (int k = 0; k < kWords; ++k) {
+        uint32_t dec = 0;
+#pragma unroll
+        for (int c = 0; c < kPer; ++c) dec |= v[k * kPer + c] << (c * TB);
+        x[k] -= dec;
+      }
+      if constexpr (kWords % 4 == 0) {
+#pragma unroll
+        for (int k = 0; k < kWords; k += 4) reinterpret_cast<uint4*>(q)[k / 4] = make_uint4(x[k], x[k + 1], x[k + 2], x[k + 3]);
+      } else if constexpr (kWords == 2) {
+        *reinterpret_cast<uint2*>(q) = make_uint2(x[0], x[1]);
+      } else {
+        *reinterpret_cast<uint32_t*>(q) = x[0];
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < kWords; ++k)
+#pragma unroll
+        for (int c = 0; c < kPer; ++c) under |= ((x[k] >> (c * TB)) & kMask) < v[k * kPer + c];
+    }
+  } else {
+    const int sh = kBits < 8 ? (int)((j * TB) & 7) : 0;  // (4 bits: the low or the high half of the byte)
+    if constexpr (kWrite) {
+      uint32_t dec = 0;
+#pragma unroll
+      for (int c = 0; c < N; ++c) dec |= v[c] << (c * TB);
+      if constexpr (kBits == 16) {
+        *reinterpret_cast<uint16_t*>(q) -= (uint16_t)dec;
+      } else if constexpr (kBits == 8) {
+        *q -= (uint8_t)dec;
+      } else if (dec) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(q);
+        atomicSub(reinterpret_cast<uint32_t*>(a & ~uintptr_t(3)), dec << (sh + 8 * (int)(a & 3)));
+      }
+    } else {
+      const uint32_t x = (kBits == 16 ? (uint32_t)*reinterpret_cast<const uint16_t*>(q) : (uint32_t)*q) >> sh;
+#pragma unroll
+      for (int c = 0; c < N; ++c) under |= ((x >> (c * TB)) & kMask) < v[c];
+    }
+  }
+  return under;
+}
+
+// counters [0, cnt) of the u32 row at d (add_hot's care at a hot row's end: the next hot row is never touched)
+template <int N, bool kWrite>
+__device__ __forceinline__ bool sub_hot(uint32_t* d, const uint32_t (&v)[N], int cnt) {
+  bool under = false;
+  if (cnt == N && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
+#pragma unroll
+    for (int k = 0; k < N; k += 4) {
+      uint4 x = reinterpret_cast<uint4*>(d)[k / 4];
+      if constexpr (kWrite) {
+        x.x -= v[k], x.y -= v[k + 1], x.z -= v[k + 2], x.w -= v[k + 3];
+        reinterpret_cast<uint4*>(d)[k / 4] = x;
+      } else {
+        under |= x.x < v[k] || x.y < v[k + 1] || x.z < v[k + 2] || x.w < v[k + 3];
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+      if (k < cnt) {
+        if constexpr (kWrite) d[k] -= v[k];
+        else under |= d[k] < v[k];
+      }
+  }
+  return under;
+}
+// (v past cnt is zero, as for add_counters)
+template <int N, bool kWrite>
+__device__ __forceinline__ bool sub_counters(const AddDst& dst, int64_t j, const uint32_t (&v)[N], int cnt) {
+  switch (dst.tb) {
+    case 32: return sub_hot<N, kWrite>(reinterpret_cast<uint32_t*>(dst.p) + j, v, cnt);
+    case 16: return sub_fields<16, N, kWrite>(dst.p, j, v);
+    case 8: return sub_fields<8, N, kWrite>(dst.p, j, v);
+    case 4: return sub_fields<4, N, kWrite>(dst.p, j, v);
+    case 2: return sub_fields<2, N, kWrite>(dst.p, j, v);
+    case 1: return sub_fields<1, N, kWrite>(dst.p, j, v);
+    default: return false;
+  }
+}
+
+// Dense image rows against dense live rows, any of the six widths on either
+// side: k_ckpt_add's mapping (a segment flagged kListBit is another kernel's,
+// or subtracts nothing).  A u32 image row faces a narrow live row here -- a
+// subtraction promotes nothing, and after the check every value fits the live
+// field.  kWrite = false: out[1] |= kBadUnder and out[2] = min(out[2], owner
+// row) where a live counter is below the image's; no store to the table.
+// out[1] |= kBadDest when a live row is a list or on the zero row (the driver
+// routes those to k_ckpt_sub_rows).
+template <bool kWrite>
+__global__ __launch_bounds__(256) void k_ckpt_sub(SegView sv, uint64_t c1, const uint8_t* src, TableView tv,
+                                                  unsigned long long* out) {
+  __shared__ uint64_t s_off[kTileChunks + 1];
+  unsigned long long bad = 0;
+  const int64_t dw = tv.dw;
+  const uint64_t tiles = (c1 + kTileChunks - 1) / kTileChunks;
+  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const uint64_t t0 = t * kTileChunks, t1 = min<uint64_t>(t0 + (uint64_t)kTileChunks, c1);
+    int64_t first;
+    int cnt;
+    tile_setup(sv, t0, s_off, first, cnt);
+    for (uint64_t c = t0 + threadIdx.x; c < t1; c += 256) {
+      const uint64_t pos = c * 16;
+      const int i = tile_find(s_off, cnt, pos);
+      const int64_t s = first + i;
+      const uint64_t rel = pos - s_off[i];
+      const uint64_t len = sv.len[s];
+      if ((len & kListBit) || rel >= len) continue;
+      const int64_t r = (int64_t)sv.addr[s];
+      const int rem = (int)min<uint64_t>(len - rel, 16);
+      const uint4 x = *reinterpret_cast<const uint4*>(src + pos);
+      const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+      if ((w[0] | w[1] | w[2] | w[3]) == 0) continue;
+      const AddDst dst = add_dst(tv, r);
+      const int sb = (int)((len * 8) / (uint64_t)dw);
+      if (dst.tb == 0) {
+        bad |= kBadDest;
+        continue;
+      }
+      bool under = false;
+      uint32_t v[16];
+      switch (sb) {
+        case 32: {
+          const uint32_t v4[4] = {w[0], w[1], w[2], w[3]};
+          under = sub_counters<4, kWrite>(dst, (int64_t)(rel >> 2), v4, rem >> 2);
+          break;
+        }
+        case 16: {
+          uint32_t v8[8];
+#pragma unroll
+          for (int q = 0; q < 8; ++q) v8[q] = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
+          under = sub_counters<8, kWrite>(dst, (int64_t)(rel >> 1), v8, rem >> 1);
+          break;
+        }
+        case 8:
+          chunk_counters<8>(w, 0, v);
+          under = sub_counters<16, kWrite>(dst, (int64_t)rel, v, 16);
+          break;
+        case 4:
+#pragma unroll 1
+          for (int g = 0; g < 2; ++g)
+            if (chunk_counters<4>(w, g, v)) under |= sub_counters<16, kWrite>(dst, (int64_t)rel * 2 + 16 * g, v, 16);
+          break;
+        case 2:
+#pragma unroll 1
+          for (int g = 0; g < 4; ++g)
+            if (chunk_counters<2>(w, g, v)) under |= sub_counters<16, kWrite>(dst, (int64_t)rel * 4 + 16 * g, v, 16);
+          break;
+        case 1:
+#pragma unroll 1
+          for (int g = 0; g < 8; ++g)
+            if (chunk_counters<1>(w, g, v)) under |= sub_counters<16, kWrite>(dst, (int64_t)rel * 8 + 16 * g, v, 16);
+          break;
+        default: bad |= kBadDest; break;
+      }
+      if (under) {
+        bad |= kBadUnder;
+        atomicMin(out + 2, (unsigned long long)r);
+      }
+    }
+    __syncthreads();
+  }
+  if (bad) atomicOr(out + 1, bad);
+}
+
+// The live list rows about to be rewritten (bound[r] != 0: the row's own
+// mass) give up their tracked bound, so k_widen_mark's new bound -- the old
+// one plus bound[r] -- is the mass itself and picks the narrowest form that
+// holds it; the rewrite leaves cbound[r] = the mass, still a bound.
+__global__ void k_ckpt_list_bounds(const uint64_t* bound, uint32_t* cbound, int64_t n) {
+  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x)
+    if (bound[r]) cbound[r] = 0u;
+}
+
+// 16 counters [j, j + 16) (j % 16 == 0) of a dense row at p8: form f < 0 (cms_forms.h), or f >= 0: u32 counters
+__device__ __forceinline__ void row_counters16(int32_t f, const uint8_t* p8, int64_t j, uint32_t (&v)[16]) {
+  if (f >= 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint4 y = reinterpret_cast<const uint4*>(p8 + 4 * j)[k];
+      v[4 * k] = y.x, v[4 * k + 1] = y.y, v[4 * k + 2] = y.z, v[4 * k + 3] = y.w;
+    }
+  } else {
+    unpack16(f, p8, j, v);
+  }
+}
+
+// Rows where either side is a list: one workgroup per listed row (rows[i], the
+// image row's payload offset off[i], its form sform[i] -- kFormList, a narrow
+// form, or 0 for u32 counters -- and a list's key count lm[i], all from the
+// validated directory).  Shapes with lists have w % 32 == 0.  Per sketch row
+// an LDS image of w u16 halves starts at the bias 2^14; every entry of a live
+// list adds one to its bucket's half, every entry of an image list takes one
+// off.  An image list holds at most kListMaxKeys = 1024 keys and the loader
+// accepts any such list -- all of them may share a bucket -- so a count can
+// pass the 2^8 that the add's u8 image relies on for built rows; u16 halves
+// around the bias hold +-1024 and no carry or borrow leaves a half.  Then each
+// lane takes groups of 16 counters: live = dense live counter (0 for a list)
+// + half - bias, image = dense image counter (0 for a list).
+//   kWrite = false  live < image anywhere: out[1] |= kBadUnder, out[2] = min(out[2], row); no store
+//   kWrite = true   image list rows only, the live row dense (widen_rows rewrote the live lists): the counts leave
+//                   through sub_counters; the workgroup owns the live row
+// The verify pass checked every image entry and the build or the loader every
+// live one; the e < w tests only keep LDS safe.
+template <bool kWrite>
+__global__ __launch_bounds__(256) void k_ckpt_sub_rows(const int32_t* rows, const uint64_t* off, const int32_t* sform,
+                                                       const uint32_t* lm, int64_t count, const uint8_t* src, TableView tv,
+                                                       int depth, unsigned long long* out) {
+  extern __shared__ uint32_t lc[];  // [w / 2]
+  constexpr uint32_t kBias = 0x4000u;
+  const int w = tv.w;
+  for (int64_t i = blockIdx.x; i < count; i += gridDim.x) {
+    const int64_t r = rows[i];
+    const int32_t sf = sform[i];
+    const uint8_t* sp = src + off[i];
+    const uint16_t* se = reinterpret_cast<const uint16_t*>(sp) + 1;
+    const uint32_t sm = sf == kFormList ? lm[i] : 0u;
+    const int32_t lf = tv.hidx[r];
+    const bool live_list = lf == kFormList;
+    const AddDst dst = add_dst(tv, r);  // (tb == 0: a list, or the zero row)
+    const bool live_zero = dst.tb == 0 && !live_list;
+    if (live_zero || (kWrite && (live_list || sf != kFormList))) {  // (uniform over the workgroup; the driver sends no such row)
+      if (threadIdx.x == 0) atomicOr(out + 1, (unsigned long long)kBadDest);
+      continue;
+    }
+    const uint32_t m_live = live_list ? tv.list_m(r) : 0u;
+    const uint16_t* le = live_list ? tv.row16(r) + 1 : nullptr;
+    bool under = false;
+    for (int rr = 0; rr < depth; ++rr) {
+      for (int j = threadIdx.x; j < (w >> 1); j += 256) lc[j] = kBias | (kBias << 16);
+      __syncthreads();
+      for (uint32_t t = threadIdx.x; t < sm; t += 256) {
+        const uint32_t b = se[(uint32_t)rr * sm + t];
+        if (b < (uint32_t)w) atomicSub(&lc[b >> 1], 1u << ((b & 1u) * 16u));
+      }
+      for (uint32_t t = threadIdx.x; t < m_live; t += 256) {
+        const uint32_t b = le[(uint32_t)rr * m_live + t];
+        if (b < (uint32_t)w) atomicAdd(&lc[b >> 1], 1u << ((b & 1u) * 16u));
+      }
+      __syncthreads();
+      for (int g = threadIdx.x; g < (w >> 4); g += 256) {
+        const int64_t j = (int64_t)rr * w + 16 * g;
+        uint32_t x[8];  // the group's 16 halves
+        uint32_t differs = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          x[k] = lc[8 * g + k];
+          differs |= x[k] ^ (kBias | (kBias << 16));
+        }
+        auto half = [&](int q) { return (q & 1) ? x[q >> 1] >> 16 : x[q >> 1] & 0xFFFFu; };
+        if constexpr (kWrite) {
+          if (!differs) continue;  // the image's list has no entry in this group
+          uint32_t dec[16];
+#pragma unroll
+          for (int q = 0; q < 16; ++q) dec[q] = kBias - half(q);
+          sub_counters<16, true>(dst, j, dec, 16);
+        } else {
+          // One side at least is a list, so at most one dense group is loaded.  An image list only takes from
+          // the bias and a live list only adds to it, so each comparison stays in 32 bits.
+          uint32_t v[16];
+          if (sf == kFormList) {
+            if (!differs) continue;  // no net entry in this group: nothing is taken from it, the live group is not read
+            if (live_list) {
+#pragma unroll
+              for (int q = 0; q < 16; ++q) under |= half(q) < kBias;
+            } else {
+              row_counters16(dst.tb == 32 ? 0 : lf, dst.p, j, v);
+#pragma unroll
+              for (int q = 0; q < 16; ++q) under |= v[q] < kBias - half(q);
+            }
+          } else {  // a dense image row against a live list: read whole, zero wherever the list has no entry
+            row_counters16(sf, sp, j, v);
+#pragma unroll
+            for (int q = 0; q < 16; ++q) under |= v[q] > half(q) - kBias;
+          }
+        }
+      }
+      __syncthreads();  // the halves are read before the next sketch row resets them
+    }
+    if (!kWrite && under) {
+      atomicOr(out + 1, (unsigned long long)kBadUnder);
+      atomicMin(out + 2, (unsigned long long)r);
     }
   }
 }
@@ -1154,6 +1487,38 @@ int load_device(cms_handle* h, const void* d_buf, int64_t bytes) {
 
 // ---- merge ----
 
+// The verify pass of a merge and of a subtraction: checksum, pad bytes and
+// every list row over the resident payload, no store.  Leaves the image's
+// segments in sg (a segment's address: its owner row, as k_ckpt_add reads it)
+// and d_out ([0] checksum, [1] kBad* flags, [2] an owner row) zeroed but [2],
+// which is all ones.
+int verify_resident(cms_handle* h, Image& im, const uint8_t* d_payload, Segs& sg, DevBuf& d_out) {
+  const Header& hd = im.hd;
+  const int64_t n = h->n;
+  im.addr.resize((size_t)n);
+  for (int64_t r = 0; r < n; ++r) im.addr[r] = (uint64_t)r;
+  build_segs(im, sg);
+  int rc = sg.upload(h);
+  if (rc) return rc;
+  unsigned long long res[2] = {0, 0};
+  const uint64_t chunks = hd.payload_bytes / 16;
+  CMS_HIP(d_out.ensure(3 * sizeof(unsigned long long)));
+  CMS_HIP(hipMemsetAsync(d_out.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
+  CMS_HIP(hipMemsetAsync(d_out.as<unsigned long long>() + 2, 0xFF, sizeof(unsigned long long), h->stream));
+  if (chunks > 0) {
+    TimedScope ts(h, "ckpt_verify");
+    hipLaunchKernelGGL(k_ckpt_unpack<false>, dim3(grid_for(h, chunks)), dim3(256), 0, h->stream, sg.view(), (uint64_t)0,
+                       chunks, d_payload, (int)h->p.depth, (int)h->p.width, d_out.as<unsigned long long>());
+    CMS_HIP(hipGetLastError());
+  }
+  CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  if (res[1] & kBadList) return set_error(CMS_E_PARAM, "checkpoint: a list row's key count or an entry is out of range");
+  if (res[1] & kBadPad) return set_error(CMS_E_PARAM, "checkpoint: padding bytes are not zero");
+  if (res[0] != hd.checksum) return set_error(CMS_E_PARAM, "checkpoint: payload checksum mismatch");
+  return CMS_OK;
+}
+
 // The image (head parsed and validated into im, payload resident at d_payload,
 // 16-byte aligned) added into the live table.  Every check -- the header-level
 // compatibility, the overflow rule, then the verify pass over the whole
@@ -1169,29 +1534,12 @@ int merge_resident(cms_handle* h, Image& im, const uint8_t* d_payload) {
   if (!h->empty) CMS_HIP(hipMemcpy(mass.data(), h->d_row_mass, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost));
   if (const char* why = check_merge_masses(hd, im.dir.data(), mass.data(), n)) return set_error(CMS_E_OVERFLOW, "%s", why);
 
-  // the verify pass: checksum, pad bytes and every list row over the resident bytes, no store
   Segs sg;
-  im.addr.resize((size_t)n);
-  for (int64_t r = 0; r < n; ++r) im.addr[r] = (uint64_t)r;  // (k_ckpt_add: a segment's owner row)
-  build_segs(im, sg);
-  int rc = sg.upload(h);
-  if (rc) return rc;
   DevBuf d_out;
   unsigned long long res[2] = {0, 0};
   const uint64_t chunks = hd.payload_bytes / 16;
-  CMS_HIP(d_out.ensure(2 * sizeof(unsigned long long)));
-  CMS_HIP(hipMemsetAsync(d_out.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
-  if (chunks > 0) {
-    TimedScope ts(h, "ckpt_verify");
-    hipLaunchKernelGGL(k_ckpt_unpack<false>, dim3(grid_for(h, chunks)), dim3(256), 0, h->stream, sg.view(), (uint64_t)0,
-                       chunks, d_payload, (int)h->p.depth, (int)h->p.width, d_out.as<unsigned long long>());
-    CMS_HIP(hipGetLastError());
-  }
-  CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
-  CMS_HIP(hipStreamSynchronize(h->stream));
-  if (res[1] & kBadList) return set_error(CMS_E_PARAM, "checkpoint: a list row's key count or an entry is out of range");
-  if (res[1] & kBadPad) return set_error(CMS_E_PARAM, "checkpoint: padding bytes are not zero");
-  if (res[0] != hd.checksum) return set_error(CMS_E_PARAM, "checkpoint: payload checksum mismatch");
+  int rc = verify_resident(h, im, d_payload, sg, d_out);
+  if (rc) return rc;
 
   // ---- every check has passed: the first write follows ----
   std::vector<int32_t> lrow;  // the image's list rows that hold entries
@@ -1283,10 +1631,165 @@ int merge_resident(cms_handle* h, Image& im, const uint8_t* d_payload) {
   return CMS_OK;
 }
 
+// The image subtracted from the live table (u32 counters).  The merge's
+// checks in the merge's order, with the mass rule turned round; then the
+// counter check over the whole image against the live rows as they are now --
+// list rows and all -- and only then the dense rewrite of the live list rows
+// that lose entries and the subtraction itself.
+int subtract_resident(cms_handle* h, Image& im, const uint8_t* d_payload) {
+  const Header& hd = im.hd;
+  const int64_t n = h->n;
+  if (const char* why = check_merge_params(hd, h->a, h->b, h->h_owner_ids.empty() ? nullptr : h->h_owner_ids.data(),
+                                           im.ids.empty() ? nullptr : im.ids.data()))
+    return set_error(CMS_E_PARAM, "checkpoint: %s", why);
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  std::vector<uint64_t> mass((size_t)n, 0);  // the live masses, then the remaining ones
+  if (!h->empty) CMS_HIP(hipMemcpy(mass.data(), h->d_row_mass, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost));
+  if (const char* why = check_subtract_masses(hd, im.dir.data(), mass.data(), n)) return set_error(CMS_E_OVERFLOW, "%s", why);
+  Segs sg;
+  DevBuf d_out;
+  const uint64_t chunks = hd.payload_bytes / 16;
+  int rc = verify_resident(h, im, d_payload, sg, d_out);
+  if (rc) return rc;
+  if (h->empty) return CMS_OK;  // every mass of the image is zero: nothing to take out of no counters
+
+  // the live rows' states (12 bytes per owner, read back once beside the masses)
+  std::vector<int32_t> hidx((size_t)n);
+  std::vector<int64_t> off((size_t)n);
+  CMS_HIP(hipMemcpy(hidx.data(), h->d_hidx, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+  CMS_HIP(hipMemcpy(off.data(), h->d_off, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost));
+  // The rows the image subtracts from, and which kernel takes each: a row
+  // whose image or live side is a list goes to k_ckpt_sub_rows (the check; in
+  // the write pass the live lists are dense, so only the image's lists do),
+  // every other to k_ckpt_sub.  Rows that subtract nothing leave the segments.
+  struct RowList {
+    std::vector<int32_t> row, form;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> m;
+    DevBuf d_row, d_form, d_off, d_m;
+    void push(int64_t r, const DirEntry& e, int depth) {
+      row.push_back((int32_t)r);
+      form.push_back(e.form == kRowHot ? 0 : table_form(e.form));
+      off.push_back(e.off);
+      m.push_back(e.form == kRowList ? (uint32_t)((e.len - 2) / (2 * (uint64_t)depth)) : 0u);
+    }
+    int upload(cms_handle* h) {
+      const size_t k = row.size();
+      if (k == 0) return CMS_OK;
+      CMS_HIP(d_row.ensure(sizeof(int32_t) * k));
+      CMS_HIP(d_form.ensure(sizeof(int32_t) * k));
+      CMS_HIP(d_off.ensure(sizeof(uint64_t) * k));
+      CMS_HIP(d_m.ensure(sizeof(uint32_t) * k));
+      CMS_HIP(hipMemcpyAsync(d_row.ptr, row.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, h->stream));
+      CMS_HIP(hipMemcpyAsync(d_form.ptr, form.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, h->stream));
+      CMS_HIP(hipMemcpyAsync(d_off.ptr, off.data(), sizeof(uint64_t) * k, hipMemcpyHostToDevice, h->stream));
+      CMS_HIP(hipMemcpyAsync(d_m.ptr, m.data(), sizeof(uint32_t) * k, hipMemcpyHostToDevice, h->stream));
+      return CMS_OK;
+    }
+  };
+  RowList crows, wrows;            // the check's and the write pass's listed rows
+  std::vector<uint64_t> len_check(sg.len), len_write(sg.len);
+  std::vector<int64_t> touched;
+  std::vector<uint64_t> bound;     // a live list row's own mass: widen_rows rewrites it densely
+  bool live_lists = false;
+  for (size_t s = 0, r = 0; s < sg.len.size(); ++s, ++r) {
+    while (im.dir[r].len == 0) ++r;
+    const DirEntry& e = im.dir[r];
+    const bool img_list = e.form == kRowList;
+    if (e.mass == 0 || (img_list && e.len <= 2)) {  // (every stored counter is zero)
+      len_check[s] |= kListBit, len_write[s] |= kListBit;
+      continue;
+    }
+    if (hidx[r] < 0 && off[r] == 0)  // (mass > 0 passed the mass rule, yet the owner has no counters)
+      return set_error(CMS_E_STATE, "cms_subtract_table: owner row %lld has a mass and no counters", (long long)r);
+    const bool live_list = hidx[r] == kFormList;
+    touched.push_back((int64_t)r);
+    if (img_list || live_list) {
+      crows.push((int64_t)r, e, hd.depth);
+      len_check[s] |= kListBit;
+    }
+    if (img_list) {
+      wrows.push((int64_t)r, e, hd.depth);
+      len_write[s] |= kListBit;
+    }
+    if (live_list) {
+      if (bound.empty()) bound.assign((size_t)n, 0);
+      bound[r] = mass[r];
+      live_lists = true;
+    }
+  }
+  unsigned long long res[3] = {0, 0, 0};
+  const size_t lds = 2 * (size_t)h->p.width;
+  auto launch = [&](bool write, RowList& rl) -> int {
+    if ((rc = rl.upload(h))) return rc;
+    TimedScope ts(h, write ? "ckpt_sub" : "ckpt_subcheck");
+    if (chunks > 0) {
+      if (write)
+        hipLaunchKernelGGL(k_ckpt_sub<true>, dim3(grid_for(h, chunks)), dim3(256), 0, h->stream, sg.view(), chunks, d_payload,
+                           h->tview(), d_out.as<unsigned long long>());
+      else
+        hipLaunchKernelGGL(k_ckpt_sub<false>, dim3(grid_for(h, chunks)), dim3(256), 0, h->stream, sg.view(), chunks, d_payload,
+                           h->tview(), d_out.as<unsigned long long>());
+    }
+    if (!rl.row.empty()) {
+      const dim3 g((unsigned)std::min<size_t>(rl.row.size(), 65536));
+      if (write)
+        hipLaunchKernelGGL(k_ckpt_sub_rows<true>, g, dim3(256), lds, h->stream, rl.d_row.as<int32_t>(), rl.d_off.as<uint64_t>(),
+                           rl.d_form.as<int32_t>(), rl.d_m.as<uint32_t>(), (int64_t)rl.row.size(), d_payload, h->tview(),
+                           (int)h->p.depth, d_out.as<unsigned long long>());
+      else
+        hipLaunchKernelGGL(k_ckpt_sub_rows<false>, g, dim3(256), lds, h->stream, rl.d_row.as<int32_t>(), rl.d_off.as<uint64_t>(),
+                           rl.d_form.as<int32_t>(), rl.d_m.as<uint32_t>(), (int64_t)rl.row.size(), d_payload, h->tview(),
+                           (int)h->p.depth, d_out.as<unsigned long long>());
+    }
+    CMS_HIP(hipGetLastError());
+    return CMS_OK;
+  };
+  // ---- the counter check: no store ----
+  sg.len = len_check;
+  if ((rc = sg.upload(h))) return rc;
+  if ((rc = launch(false, crows))) return rc;
+  CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  if (res[1] & kBadDest) return set_error(CMS_E_STATE, "cms_subtract_table: a live row changed form under the call");
+  if (res[1] & kBadUnder)
+    return set_error(CMS_E_OVERFLOW, "owner row %lld: a counter would fall below zero (the image is no part of this table's stream)",
+                     (long long)res[2]);
+
+  // ---- every check has passed: the first write follows ----
+  DevBuf d_touched;
+  if (live_lists) {  // bound > 0 on a list row is a rewrite (widen_needed); every other row's bound is 0: not listed
+    CMS_HIP(h->ws_bound.ensure(sizeof(uint64_t) * (size_t)n));
+    CMS_HIP(hipMemcpyAsync(h->ws_bound.ptr, bound.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_ckpt_list_bounds, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192))),
+                       dim3(256), 0, h->stream, h->ws_bound.as<uint64_t>(), h->d_cbound, n);
+    CMS_HIP(hipGetLastError());
+    if ((rc = widen_rows(h, h->ws_bound.as<uint64_t>(), nullptr, false))) return rc;
+  }
+  if (h->rf_valid && !touched.empty()) {
+    CMS_HIP(d_touched.ensure(sizeof(int64_t) * touched.size()));
+    CMS_HIP(hipMemcpyAsync(d_touched.ptr, touched.data(), sizeof(int64_t) * touched.size(), hipMemcpyHostToDevice, h->stream));
+    if ((rc = refresh_mark(h, d_touched.as<int64_t>(), (int64_t)touched.size()))) return rc;
+  }
+  sg.len = len_write;
+  if ((rc = sg.upload(h))) return rc;
+  if ((rc = launch(true, wrows))) return rc;
+  for (int64_t r = 0; r < n; ++r) mass[r] -= im.dir[r].mass;
+  CMS_HIP(hipMemcpyAsync(h->d_row_mass, mass.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  h->pairs_ingested = h->pairs_ingested > hd.pairs_ingested ? h->pairs_ingested - hd.pairs_ingested : 0;
+  h->norms_valid = false;
+  h->finalized = false;
+  h->stale_possible = true;
+  if (res[1] & kBadDest) return set_error(CMS_E_STATE, "cms_subtract_table: a live row was in no form to give up its counters");
+  return CMS_OK;
+}
+
 // The file is staged whole in device memory (through two pinned buffers), then
-// merged as a device image: the verify pass must see all of it before the
+// merged (or subtracted) as a device image: the verify pass must see all of it before the
 // first write, and a list row may straddle any staging boundary.
-int merge_file(cms_handle* h, const char* path) {
+int merge_file(cms_handle* h, const char* path, bool subtract = false) {
   File in;
   in.f = std::fopen(path, "rb");
   if (!in.f) return set_error(CMS_E_PARAM, "cannot open %s", path);
@@ -1310,7 +1813,8 @@ int merge_file(cms_handle* h, const char* path) {
   DevBuf payload;
   if (payload.ensure((size_t)std::max<uint64_t>(hd.payload_bytes, 16)) != hipSuccess) {
     (void)hipGetLastError();
-    return set_error(CMS_E_OOM, "cms_merge_table: no device memory to stage the %.2f GB image", 1e-9 * (double)hd.payload_bytes);
+    return set_error(CMS_E_OOM, "%s: no device memory to stage the %.2f GB image", subtract ? "cms_subtract_table" : "cms_merge_table",
+                     1e-9 * (double)hd.payload_bytes);
   }
   const uint64_t nchunks = (hd.payload_bytes + kIoChunk - 1) / kIoChunk;
   if (nchunks > 0) {
@@ -1328,10 +1832,10 @@ int merge_file(cms_handle* h, const char* path) {
     CMS_HIP(hipStreamSynchronize(h->side_stream));
     add_host_time(h, "ckpt_io", t_io);
   }
-  return merge_resident(h, im, payload.as<uint8_t>());
+  return subtract ? subtract_resident(h, im, payload.as<uint8_t>()) : merge_resident(h, im, payload.as<uint8_t>());
 }
 
-int merge_device(cms_handle* h, const void* d_buf, int64_t bytes) {
+int merge_device(cms_handle* h, const void* d_buf, int64_t bytes, bool subtract = false) {
   if (bytes < (int64_t)sizeof(Header)) return set_error(CMS_E_PARAM, "checkpoint image: shorter than a checkpoint header");
   if (reinterpret_cast<uintptr_t>(d_buf) & 15) return set_error(CMS_E_PARAM, "device image must be 16-byte aligned");
   CMS_HIP(hipStreamSynchronize(h->stream));
@@ -1348,7 +1852,8 @@ int merge_device(cms_handle* h, const void* d_buf, int64_t bytes) {
       return set_error(CMS_E_PARAM, "checkpoint image changed while it was read");
     if ((rc = parse_head(head.data(), im))) return rc;
   }
-  return merge_resident(h, im, static_cast<const uint8_t*>(d_buf) + hd.payload_off);
+  const uint8_t* d_payload = static_cast<const uint8_t*>(d_buf) + hd.payload_off;
+  return subtract ? subtract_resident(h, im, d_payload) : merge_resident(h, im, d_payload);
 }
 
 }  // namespace
@@ -1408,6 +1913,31 @@ int cms_merge_table_device(cms_handle* h, const void* d_buf, int64_t bytes) {
   Guard g(h);
   if (int rc = check_receives_image(h, "cms_merge_table_device")) return rc;
   return merge_device(h, d_buf, bytes);
+}
+
+// (an fp64 subtraction is no inverse of the reference's rounded adds)
+static int check_subtracts(cms_handle* h, const char* what) {
+  if (int rc = check_receives_image(h, what)) return rc;
+  if (h->f64)
+    return set_error(CMS_E_STATE, "%s: fp64 counters do not subtract: (a + b) - b is not a in fp64, so the result would be no stream's table",
+                     what);
+  return CMS_OK;
+}
+
+int cms_subtract_table(cms_handle* h, const char* path) {
+  if (!h || !path) return set_error(CMS_E_PARAM, "null argument");
+  if (int rc = cms_synchronize(h)) return rc;  // a pending device-ingest error comes first: nothing is subtracted
+  Guard g(h);
+  if (int rc = check_subtracts(h, "cms_subtract_table")) return rc;
+  return merge_file(h, path, true);
+}
+
+int cms_subtract_table_device(cms_handle* h, const void* d_buf, int64_t bytes) {
+  if (!h || !d_buf) return set_error(CMS_E_PARAM, "null argument");
+  if (int rc = cms_synchronize(h)) return rc;
+  Guard g(h);
+  if (int rc = check_subtracts(h, "cms_subtract_table_device")) return rc;
+  return merge_device(h, d_buf, bytes, true);
 }
 
 int cms_checkpoint_info(const char* path, cms_params* out, int64_t* file_bytes) {

@@ -579,6 +579,24 @@ class SketchTable:
         torch.cuda.current_stream(image.device).synchronize()  # its producers are done
         check(self._lib.cms_merge_table_device(self._h, ctypes.c_void_p(image.data_ptr()), int(image.numel())))
 
+    def subtract(self, path):
+        """A checkpoint file subtracted from this table, counter by counter
+        (cms_subtract_table): the table of the stream that remains, when the
+        file's stream is a part of this table's.  u32 counters only; the rules
+        of merge() apply, and no row mass and no counter may fall below zero
+        (CMS_E_OVERFLOW).  A refused subtraction changes nothing; finalize()
+        afterwards re-derives the norms."""
+        check(self._lib.cms_subtract_table(self._h, os.fsencode(path)))
+
+    def subtract_device(self, image):
+        """subtract() of a checkpoint image (uint8 tensor on the handle's
+        device, as save_device() returns it; cms_subtract_table_device)."""
+        import torch
+        if image.device != torch.device("cuda", self.device) or image.dtype != torch.uint8 or not image.is_contiguous():
+            raise ValueError("image must be a contiguous uint8 tensor on cuda:%d" % self.device)
+        torch.cuda.current_stream(image.device).synchronize()  # its producers are done
+        check(self._lib.cms_subtract_table_device(self._h, ctypes.c_void_p(image.data_ptr()), int(image.numel())))
+
     @classmethod
     def from_checkpoint(cls, path, device=-1, weighted=False):
         """A new handle of the file's shape (cms_checkpoint_info), loaded from it."""
