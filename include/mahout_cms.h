@@ -404,6 +404,66 @@ int cms_read_counters_device(cms_handle* h, int64_t row_begin, int64_t row_count
 #define CMS_FORM_LIST 6 /* sparse key-bucket list */
 int cms_owner_forms(cms_handle* h, int64_t row_begin, int64_t row_count, int32_t* out_form, uint32_t* out_bound);
 
+/* ---- anonymous profiles: queries for a user the table does not hold ---------
+ * PlusAnonymousUserDataModel (T/impl/model/PlusAnonymousUserDataModel.java:74-137,
+ * TEMP_USER_ID = Long.MIN_VALUE) lets recommender.recommend(TEMP_USER_ID, n)
+ * serve temporary preferences -- a visitor's session, a new user, a basket.
+ * With CosineCM that call sketches the preferences with exportProfile
+ * (CosineCM.java:41-58) and compares the sketch with every owner's (:83-96).
+ * These calls take the preferences themselves: (keys[i], vals[i]) pairs,
+ * update(key, val) each in order, duplicate keys adding; vals NULL = 1.0 each.
+ *
+ * The handle must be finalized (CMS_E_STATE), with a fixed shape and
+ * CMS_COUNTER_U32: per-owner-shape handles and fp64 handles return CMS_E_STATE
+ * (both need kernel families of their own, not built yet).  A merged
+ * multi-rank handle answers locally -- every rank holds the whole table, no
+ * collective is issued.  The calls hold the handle exclusively, as
+ * cms_most_similar does, and change nothing of it: not the table, the norms,
+ * the kept refresh lists or touched marks, pairs_ingested or any cms_stats
+ * field (topk_redo aside, when the top-k's radix fallback runs).
+ *
+ * Values are validated as a host ingest validates them -- a non-negative
+ * multiple of 2^-frac_bits below 2^(32-frac_bits), else CMS_E_VALUE; a profile
+ * whose total in counter units reaches 2^32 is CMS_E_OVERFLOW -- for the whole
+ * batch before any device work: a refused call writes no output.  An empty
+ * profile is legal: every similarity NaN, an empty list, every estimate NaN.
+ * A width whose sketch row does not fit a compute unit's LDS as u32 counters
+ * (above 32768) is CMS_E_PARAM.
+ *
+ * Every similarity equals, bit for bit, what cms_similarities returns for a
+ * twin owner holding the same stream (DoubleCountMinSketch.cosine :114-149,
+ * then normalizeWeightResult). */
+
+/* CosineCM.userSimilarity(TEMP_USER_ID, ids2[i]) for the temporary preferences
+ * (keys[0..m), vals[0..m) or NULL = 1.0 each).  CMS_E_NO_SUCH_ID for an
+ * unknown owner. */
+int cms_anonymous_similarities(cms_handle* h, const int64_t* keys, const float* vals, int64_t m,
+                               const int64_t* ids2, int64_t n, double* out);
+/* GenericUserBasedRecommender.mostSimilarUserIDs(TEMP_USER_ID, k) (:119-127)
+ * with TopItems.getTopUsers (TopItems.java:91-136) for nq profiles at once:
+ * profile q is keys/vals[offsets[q] .. offsets[q+1]) (nq + 1 offsets from 0,
+ * non-decreasing, else CMS_E_PARAM); ids/scores [nq][k], counts[nq].  Every
+ * owner is a candidate -- there is no self to exclude, an owner identical to
+ * the profile is listed at its score -- in the order similarity descending,
+ * owner ID ascending, NaN excluded.  k <= 512; entries past counts[q] are
+ * padded as cms_top_k_all pads them (ID -1, all-ones NaN).  Each owner's
+ * stored row is read once per batch of profiles, not once per profile. */
+int cms_anonymous_most_similar(cms_handle* h, int64_t nq, const int64_t* offsets, const int64_t* keys,
+                               const float* vals, int32_t k, int64_t* ids, double* scores, int32_t* counts);
+/* doEstimatePreference(TEMP_USER_ID, neighbourhood, item)
+ * (GenericUserBasedRecommender.java:134-184) for q items: the similarities of
+ * the temporary preferences with neighbor_ids[0..mn) in the caller's order,
+ * then cms_estimate_preferences' sums.  The temporary user is never in its own
+ * neighbourhood.  CMS_E_NO_SUCH_ID for an unknown neighbour. */
+int cms_anonymous_estimate_preferences(cms_handle* h, const int64_t* keys, const float* vals, int64_t m,
+                                       const int64_t* neighbor_ids, int64_t mn, const int64_t* item_keys, int64_t q,
+                                       int32_t use_capper, float cap_min, float cap_max, float* out);
+/* How many profiles the similarity kernel serves per read of an owner's row at
+ * this handle's width: *batch for sketch-row images of elem_bytes (2: every
+ * counter of the batch below 2^16, else 4) -- the largest power of two up to
+ * 8 whose [width][batch] image fits 128 KiB of LDS.  For tests and sizing. */
+int cms_anonymous_batch(cms_handle* h, int32_t elem_bytes, int32_t* batch);
+
 /* ---- per-owner sketch shapes: CosineCM with its CountMinSketchConfig --------
  * The reference sizes every owner's sketch separately.  CountMinSketchConfig
  * (T/impl/common/CountMinSketchConfig.java:120-158) picks (d, w) per owner and

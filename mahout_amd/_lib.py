@@ -47,6 +47,8 @@ EXPORTS = [
     "cms_top_k_all_device", "cms_top_k_refresh_device", "cms_set_hash_params", "cms_recommend_batch",
     "cms_checkpoint_size", "cms_save_table", "cms_load_table", "cms_save_table_device", "cms_load_table_device",
     "cms_checkpoint_info", "cms_merge_table", "cms_merge_table_device", "cms_subtract_table", "cms_subtract_table_device",
+    "cms_anonymous_similarities", "cms_anonymous_most_similar", "cms_anonymous_estimate_preferences",
+    "cms_anonymous_batch",
 ]
 
 
@@ -177,6 +179,11 @@ _SIGS = {
     "cms_subtract_table": (_int, [_vp, ctypes.c_char_p]),
     "cms_subtract_table_device": (_int, [_vp, _vp, _i64]),
     "cms_checkpoint_info": (_int, [ctypes.c_char_p, ctypes.POINTER(CmsParams), ctypes.POINTER(_i64)]),
+    "cms_anonymous_similarities": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "cms_anonymous_most_similar": (_int, [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "cms_anonymous_estimate_preferences": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, ctypes.c_float,
+                                                  ctypes.c_float, _vp]),
+    "cms_anonymous_batch": (_int, [_vp, _i32, ctypes.POINTER(_i32)]),
 }
 
 _lib = None

@@ -16,6 +16,7 @@
 #include <new>
 #include <vector>
 
+#include "cms_anon.h"
 #include "cms_internal.h"
 
 namespace cms {
@@ -794,7 +795,8 @@ int cms_release_scratch(cms_handle* h) {
                   &h->ws_csr_key, &h->ws_csr_val, &h->ws_csr_off, &h->ws_csr_hi, &h->ws_hotpart, &h->ws_hist, &h->ws_hot, &h->ws_query,
                   &h->ws_out, &h->ws_slab, &h->ws_topq, &h->ws_tiles, &h->ws_cand, &h->ws_srow,
                   &h->ws_mbnd, &h->ws_mbits, &h->ws_mwoff, &h->ws_mpacked, &h->rf_ids, &h->rf_sc, &h->rf_cnt,
-                  &h->rf_full, &h->rf_touch, &h->rf_new, &h->rf_redo, &h->rf_perm};
+                  &h->rf_full, &h->rf_touch, &h->rf_new, &h->rf_redo, &h->rf_perm,
+                  &h->an_in, &h->an_sk, &h->an_nz, &h->an_meta, &h->an_rows, &h->an_out};
   for (DevBuf* b : ws) b->release();
   // the kept refresh lists and touched marks are gone: the next COO ingest must not mark
   // into rf_touch, and the next cms_top_k_refresh is a whole job
@@ -1300,6 +1302,133 @@ int cms_top_k_rows(cms_handle* h, int64_t row_begin, int64_t row_count, int32_t 
   if (row_begin < 0 || row_count < 0 || row_begin + row_count > h->n) return set_error(CMS_E_PARAM, "row range");
   if (row_count == 0) return CMS_OK;
   return top_k_host(h, row_begin, row_count, k, ids, scores, counts);
+}
+
+// ---- anonymous profiles (cms_anonymous.hip) ----
+
+// the state every anonymous call needs, and the batch's validation -- all on
+// the host, before any device work
+static int anon_require(cms_handle* h, const char* what, int64_t nq, const int64_t* offsets, const float* vals) {
+  if (h->per_owner)
+    return set_error(CMS_E_STATE, "%s: not available on a per-owner-shape handle (cms_create_per_owner)", what);
+  if (h->f64) return set_error(CMS_E_STATE, "%s: not available on an fp64-counter handle (CMS_COUNTER_F64)", what);
+  if (int rc = require_finalized(h)) return rc;
+  if (anon_batch_size(h->p.width, 4) == 0)
+    return set_error(CMS_E_PARAM, "%s: width %d is beyond the LDS image of one profile's sketch row", what,
+                     h->p.width);
+  switch (anon_validate_batch(nq, offsets, vals, h->p.frac_bits)) {
+    case kAnonOk: return CMS_OK;
+    case kAnonParam: return set_error(CMS_E_PARAM, "%s: offsets must start at 0 and never decrease", what);
+    case kAnonValue:
+      return set_error(CMS_E_VALUE, "%s: u32 counters need non-negative multiples of 2^-frac_bits below 2^(32-frac_bits)",
+                       what);
+    default: return set_error(CMS_E_OVERFLOW, "%s: a profile's total increment reached 2^32 (u32 counters)", what);
+  }
+}
+
+// the similarities of one profile with the owner rows `rows` [n], left on the
+// device in h->an_out (doubles) with the rows in h->an_rows
+static int anon_one_profile(cms_handle* h, const int64_t* keys, const float* vals, int64_t m,
+                            const std::vector<int64_t>& rows) {
+  const int64_t n = (int64_t)rows.size();
+  const int64_t off[2] = {0, m};
+  AnonBatch ab;
+  int rc;
+  if ((rc = anon_upload(h, 1, off, keys, vals, ab))) return rc;
+  CMS_HIP(h->an_rows.ensure(sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1)));
+  CMS_HIP(h->an_out.ensure(sizeof(double) * (size_t)std::max<int64_t>(n, 1)));
+  if (n > 0)
+    CMS_HIP(hipMemcpyAsync(h->an_rows.ptr, rows.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  if ((rc = anon_build(h, ab, 0, 1))) return rc;
+  return anon_cosines(h, ab, h->an_rows.as<int64_t>(), n, h->an_out.as<double>(), n);
+}
+
+int cms_anonymous_similarities(cms_handle* h, const int64_t* keys, const float* vals, int64_t m, const int64_t* ids2,
+                               int64_t n, double* out) {
+  if (!h || m < 0 || n < 0 || (m > 0 && !keys) || (n > 0 && (!ids2 || !out)))
+    return set_error(CMS_E_PARAM, "null argument");
+  Guard g(h);
+  const int64_t off[2] = {0, m};
+  int rc = anon_require(h, "cms_anonymous_similarities", 1, off, vals);
+  if (rc) return rc;
+  std::vector<int64_t> rows((size_t)n);
+  for (int64_t i = 0; i < n; ++i)
+    if ((rc = row_of(h, ids2[i], &rows[(size_t)i]))) return rc;
+  if (n == 0) return CMS_OK;
+  if ((rc = anon_one_profile(h, keys, vals, m, rows))) return rc;
+  CMS_HIP(hipMemcpyAsync(out, h->an_out.ptr, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  return CMS_OK;
+}
+
+int cms_anonymous_estimate_preferences(cms_handle* h, const int64_t* keys, const float* vals, int64_t m,
+                                       const int64_t* neighbor_ids, int64_t mn, const int64_t* item_keys, int64_t q,
+                                       int32_t use_capper, float cap_min, float cap_max, float* out) {
+  if (!h || m < 0 || mn < 0 || q < 0 || (m > 0 && !keys) || (mn > 0 && !neighbor_ids) || (q > 0 && (!item_keys || !out)))
+    return set_error(CMS_E_PARAM, "null argument");
+  Guard g(h);
+  const int64_t off[2] = {0, m};
+  int rc = anon_require(h, "cms_anonymous_estimate_preferences", 1, off, vals);
+  if (rc) return rc;
+  std::vector<int64_t> rows((size_t)mn);
+  for (int64_t i = 0; i < mn; ++i)
+    if ((rc = row_of(h, neighbor_ids[i], &rows[(size_t)i]))) return rc;
+  if (q == 0) return CMS_OK;
+  if ((rc = anon_one_profile(h, keys, vals, m, rows))) return rc;
+  CMS_HIP(h->ws_query.ensure(sizeof(int64_t) * (size_t)q));
+  CMS_HIP(h->ws_out.ensure(sizeof(float) * (size_t)q));
+  CMS_HIP(hipMemcpyAsync(h->ws_query.ptr, item_keys, sizeof(int64_t) * (size_t)q, hipMemcpyHostToDevice, h->stream));
+  // user_row -1: no neighbour is the temporary user
+  if ((rc = estimate_preferences(h, -1, h->an_rows.as<int64_t>(), h->an_out.as<double>(), mn, h->ws_query.as<int64_t>(),
+                                 q, use_capper, cap_min, cap_max, h->ws_out.as<float>())))
+    return rc;
+  CMS_HIP(hipMemcpyAsync(out, h->ws_out.ptr, sizeof(float) * (size_t)q, hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  return CMS_OK;
+}
+
+int cms_anonymous_most_similar(cms_handle* h, int64_t nq, const int64_t* offsets, const int64_t* keys,
+                               const float* vals, int32_t k, int64_t* ids, double* scores, int32_t* counts) {
+  if (!h || nq < 0 || (nq > 0 && (!offsets || !ids || !counts))) return set_error(CMS_E_PARAM, "null argument");
+  if (k < 1 || k > kCandCap / 2) return set_error(CMS_E_PARAM, "k must be in [1, %d]", kCandCap / 2);
+  if (nq > 0 && offsets[0] == 0 && offsets[nq] > 0 && !keys) return set_error(CMS_E_PARAM, "null argument");
+  Guard g(h);
+  int rc = anon_require(h, "cms_anonymous_most_similar", nq, offsets, vals);
+  if (rc) return rc;
+  if (nq == 0) return CMS_OK;
+  const int64_t n = h->n;
+  DevBuf o_ids, o_sc, o_cnt;
+  const size_t cells = (size_t)nq * (size_t)k;
+  CMS_HIP(o_ids.ensure(sizeof(int64_t) * cells));
+  CMS_HIP(o_sc.ensure(sizeof(double) * cells));
+  CMS_HIP(o_cnt.ensure(sizeof(int32_t) * (size_t)nq));
+  CMS_HIP(hipMemsetAsync(o_ids.ptr, 0xFF, sizeof(int64_t) * cells, h->stream));  // padding: ID -1, all-ones NaN
+  CMS_HIP(hipMemsetAsync(o_sc.ptr, 0xFF, sizeof(double) * cells, h->stream));
+  AnonBatch ab;
+  if ((rc = anon_upload(h, nq, offsets, keys, vals, ab))) return rc;
+  const int64_t chunk = anon_chunk_rows(h);
+  for (int64_t c0 = 0; c0 < nq; c0 += chunk) {
+    const int64_t qc = std::min<int64_t>(chunk, nq - c0);
+    if ((rc = anon_build(h, ab, c0, qc))) return rc;
+    CMS_HIP(h->ws_slab.ensure(sizeof(double) * (size_t)(qc * n)));
+    if ((rc = anon_cosines(h, ab, nullptr, n, h->ws_slab.as<double>(), n))) return rc;
+    std::vector<TopQuery> qs((size_t)qc);
+    for (int64_t q = 0; q < qc; ++q) qs[(size_t)q] = TopQuery{q, -1, c0 + q};  // self_col -1: no column is excluded
+    if ((rc = launch_top_k(h, h->ws_slab.as<double>(), qs, k, nullptr, o_ids.as<int64_t>(), o_sc.as<double>(),
+                           o_cnt.as<int32_t>())))
+      return rc;
+  }
+  CMS_HIP(hipMemcpyAsync(ids, o_ids.ptr, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, h->stream));
+  if (scores) CMS_HIP(hipMemcpyAsync(scores, o_sc.ptr, sizeof(double) * cells, hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipMemcpyAsync(counts, o_cnt.ptr, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  return CMS_OK;
+}
+
+int cms_anonymous_batch(cms_handle* h, int32_t elem_bytes, int32_t* batch) {
+  if (!h || !batch || (elem_bytes != 2 && elem_bytes != 4)) return set_error(CMS_E_PARAM, "bad argument");
+  *batch = anon_batch_size(h->p.width, elem_bytes);
+  return CMS_OK;
 }
 
 extern "C++" {

@@ -362,6 +362,11 @@ struct cms_handle {
   cms::DevBuf ws_hist, ws_small, ws_partials, ws_hot;
   cms::DevBuf ws_query, ws_query2, ws_out, ws_srow, ws_f4, ws_i8blk;
   cms::DevBuf ws_limb0, ws_limbmeta, ws_limbhot, ws_hotlist, ws_tiles, ws_slab, ws_topq, ws_nsq, ws_cand;
+  // anonymous-profile queries (cms_anonymous.hip): the batch as uploaded
+  // (offsets, keys, values), a chunk's sketches [Q][d][w], their non-zero
+  // bucket lists [Q][d][w], the per-(profile, row) norms / square roots / list
+  // lengths and per-profile maxima, the explicit owner rows, the outputs
+  cms::DevBuf an_in, an_sk, an_nz, an_meta, an_rows, an_out;
 
   // communicator: RCCL (cms_comm_init) or a caller transport (cms_comm_init_transport)
   ncclComm_t comm = nullptr;
@@ -652,6 +657,26 @@ int launch_top_k(cms_handle* h, const double* slab, const std::vector<TopQuery>&
 int64_t slab_rows_for(int64_t n);
 // slab rows of one multi-limb chunk of the all-pairs job (memory permitting, up to 4096 at 1M)
 int64_t multi_slab_rows(cms_handle* h, int64_t n);
+// ---- cms_anonymous.hip: profiles that are no row of the table ----
+// A validated batch of nq profiles (host CSR; vals may be null) on the device.
+struct AnonBatch {
+  int64_t nq = 0, npairs = 0;
+  const int64_t* d_off = nullptr;
+  const int64_t* d_keys = nullptr;
+  const float* d_vals = nullptr;
+  // the chunk built last: profiles [c0, c0 + qc), their largest counters and longest bucket lists
+  int64_t c0 = 0, qc = 0;
+  std::vector<uint32_t> qmax, qnnz;
+};
+int anon_upload(cms_handle* h, int64_t nq, const int64_t* offsets, const int64_t* keys, const float* vals,
+                AnonBatch& ab);
+// profiles per chunk: the slab budget (slab_rows_for) and the sketch scratch
+int64_t anon_chunk_rows(cms_handle* h);
+// sketches, norms and bucket lists of profiles [c0, c0 + qc) (synchronises)
+int anon_build(cms_handle* h, AnonBatch& ab, int64_t c0, int64_t qc);
+// userSimilarity(profile c0 + q, owner row d_rows[t] (null: row t)) for q < qc,
+// t < ncols into d_out[q * ld + t]
+int anon_cosines(cms_handle* h, const AnonBatch& ab, const int64_t* d_rows, int64_t ncols, double* d_out, int64_t ld);
 // ---- cms_f64.hip (CMS_COUNTER_F64) ----
 int f64_ingest_csr(cms_handle* h, const int64_t* d_off, const int64_t* d_key, const float* d_val);
 int f64_ingest_coo_host(cms_handle* h, const int64_t* owner, const int64_t* key, const float* val, int64_t np);

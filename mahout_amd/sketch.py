@@ -294,6 +294,76 @@ class SketchTable:
                                                  int(capper is not None), float(lo), float(hi), _ptr(out)))
         return out
 
+    # -- anonymous profiles: preferences that are no row of the table --
+    @staticmethod
+    def _profile(keys, vals):
+        keys = np.ascontiguousarray(keys, np.int64).reshape(-1)
+        if vals is not None:
+            vals = np.ascontiguousarray(vals, np.float32).reshape(-1)
+            if vals.size != keys.size:
+                raise ValueError("keys and vals differ in length")
+        return keys, vals
+
+    def anonymous_similarities(self, keys, vals, ids2):
+        """CosineCM.userSimilarity(TEMP_USER_ID, ids2[i]) for the temporary
+        preferences (keys, vals; vals None = 1.0 each)."""
+        keys, vals = self._profile(keys, vals)
+        ids2 = np.ascontiguousarray(ids2, np.int64)
+        out = np.zeros(ids2.size, np.float64)
+        check(self._lib.cms_anonymous_similarities(self._h, _ptr(keys), _ptr(vals), keys.size, _ptr(ids2), ids2.size,
+                                                   _ptr(out)))
+        return out
+
+    def anonymous_most_similar(self, profiles, k):
+        """mostSimilarUserIDs(TEMP_USER_ID, k) for many profiles at once.
+        profiles: (offsets, keys, vals) in CSR form (vals may be None), or a
+        list of (keys, vals) pairs.  Returns ids [nq][k], scores [nq][k]
+        (padding: ID -1, NaN) and counts [nq], as top_k_rows does."""
+        if isinstance(profiles, tuple) and len(profiles) == 3 and not isinstance(profiles[0], tuple):
+            offsets, keys, vals = profiles
+            offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+            keys, vals = self._profile(keys, vals)
+        else:
+            plist = [self._profile(kk, vv) for kk, vv in profiles]
+            offsets = np.zeros(len(plist) + 1, np.int64)
+            np.cumsum([p[0].size for p in plist], out=offsets[1:])
+            keys = np.concatenate([p[0] for p in plist]) if plist else np.zeros(0, np.int64)
+            with_vals = [p[1] is not None for p in plist]
+            if any(with_vals):  # a profile without values reads as 1.0 each
+                vals = np.concatenate([p[1] if p[1] is not None else np.ones(p[0].size, np.float32) for p in plist])
+            else:
+                vals = None
+        if offsets.size < 1:
+            raise ValueError("offsets needs nq + 1 entries")
+        nq = offsets.size - 1
+        if nq > 0 and (keys.size < int(offsets.max()) or (vals is not None and vals.size != keys.size)):
+            raise ValueError("offsets reach past the keys")
+        ids = np.zeros((nq, k), np.int64)
+        sc = np.zeros((nq, k), np.float64)
+        cnt = np.zeros(nq, np.int32)
+        check(self._lib.cms_anonymous_most_similar(self._h, nq, _ptr(offsets), _ptr(keys), _ptr(vals), int(k),
+                                                   _ptr(ids), _ptr(sc), _ptr(cnt)))
+        return ids, sc, cnt
+
+    def anonymous_estimate_preferences(self, keys, vals, neighbor_ids, item_keys, capper=None):
+        """doEstimatePreference(TEMP_USER_ID, neighbourhood, item) for every
+        item key; capper = (min, max) or None."""
+        keys, vals = self._profile(keys, vals)
+        nb = np.ascontiguousarray(neighbor_ids, np.int64)
+        it = np.ascontiguousarray(item_keys, np.int64)
+        out = np.zeros(it.size, np.float32)
+        lo, hi = capper if capper is not None else (0.0, 0.0)
+        check(self._lib.cms_anonymous_estimate_preferences(self._h, _ptr(keys), _ptr(vals), keys.size, _ptr(nb),
+                                                           nb.size, _ptr(it), it.size, int(capper is not None),
+                                                           float(lo), float(hi), _ptr(out)))
+        return out
+
+    def anonymous_batch(self, elem_bytes=2):
+        """Profiles the similarity kernel serves per read of an owner's row."""
+        b = ctypes.c_int32()
+        check(self._lib.cms_anonymous_batch(self._h, int(elem_bytes), ctypes.byref(b)))
+        return b.value
+
     def estimate_preferences_batch(self, user_ids, nb_offsets, neighbor_ids, item_offsets, item_keys, capper=None):
         """estimate_preferences for many users in one call
         (cms_estimate_preferences_batch): user u's neighbourhood is

@@ -133,12 +133,91 @@ def _map_error(e, owner_kind="user"):
     return TasteException(str(e))
 
 
+class PlusAnonymousUserDataModel:
+    """PlusAnonymousUserDataModel(delegate)
+    (T/impl/model/PlusAnonymousUserDataModel.java:74-137): the delegate's
+    users plus one temporary user, TEMP_USER_ID, whose preferences are set
+    for the length of a request -- recommender.recommend(TEMP_USER_ID, n)
+    then serves a user the model does not hold.  Over such a model CosineCM
+    keeps the delegate's sketch table and answers for TEMP_USER_ID with the
+    anonymous-profile calls (SketchTable.anonymous_*); the temporary
+    preferences take the table's own frac_bits scaling, and values it cannot
+    hold raise TasteException."""
+
+    TEMP_USER_ID = -2 ** 63  # Long.MIN_VALUE
+
+    def __init__(self, delegate):
+        self._delegate = delegate
+        self._temp = None  # (item IDs, float32 values) as given
+
+    def getDelegate(self):
+        return self._delegate
+
+    def setTempPrefs(self, itemIDs, values):
+        keys = np.ascontiguousarray(itemIDs, np.int64).reshape(-1)
+        vals = np.ascontiguousarray(values, np.float32).reshape(-1)
+        if keys.size == 0 or keys.size != vals.size:
+            raise ValueError("prefs is null or empty")
+        self._temp = (keys, vals)
+
+    def clearTempPrefs(self):
+        self._temp = None
+
+    def _temp_prefs(self):
+        if self._temp is None:
+            raise NoSuchUserException(self.TEMP_USER_ID)
+        return self._temp
+
+    def getUserIDs(self):
+        ids = self._delegate.getUserIDs()
+        if self._temp is None:
+            return ids
+        return np.concatenate([np.array([self.TEMP_USER_ID], np.int64), np.asarray(ids, np.int64)])
+
+    def getPreferencesFromUser(self, user_id):
+        if user_id == self.TEMP_USER_ID:
+            return self._temp_prefs()
+        return self._delegate.getPreferencesFromUser(user_id)
+
+    def getItemIDsFromUser(self, user_id):
+        if user_id == self.TEMP_USER_ID:
+            return self._temp_prefs()[0]
+        return self._delegate.getPreferencesFromUser(user_id)[0]
+
+    def getPreferenceValue(self, user_id, item_id):
+        if user_id == self.TEMP_USER_ID:
+            keys, vals = self._temp_prefs()
+            hit = np.nonzero(keys == item_id)[0]
+            return float(vals[hit[0]]) if hit.size else None
+        return self._delegate.getPreferenceValue(user_id, item_id)
+
+    def getItemIDs(self):
+        return self._delegate.getItemIDs()
+
+    def getNumItems(self):
+        return self._delegate.getNumItems()
+
+    def getNumUsers(self):
+        return self._delegate.getNumUsers() + (0 if self._temp is None else 1)
+
+    def hasPreferenceValues(self):
+        return self._delegate.hasPreferenceValues()
+
+    def getMinPreference(self):
+        return self._delegate.getMinPreference()
+
+    def getMaxPreference(self):
+        return self._delegate.getMaxPreference()
+
+
 class CosineCM:
     """CosineCM(DataModel, [Weighting,] CountMinSketchConfig, HashFunctionBuilder).
 
     Owners are the DataModel's users (sketches keyed by item ID).  Over a
     transposed DataModel the owners are items and userSimilarity /
-    itemSimilarity are the sketch-cosine ItemSimilarity.
+    itemSimilarity are the sketch-cosine ItemSimilarity.  Over a
+    PlusAnonymousUserDataModel the owners are the delegate's users, and
+    TEMP_USER_ID is answered from the temporary preferences.
     """
 
     def __init__(self, dataModel, conf, hfBuilder, weighting=Weighting.UNWEIGHTED, device=-1, sketches=None):
@@ -156,6 +235,10 @@ class CosineCM:
             width = depth = None  # each owner has its own shape
         else:
             width, depth = conf.shape() if hasattr(conf, "shape") else (conf.width, conf.depth)
+        # the table holds the delegate's users; the temporary user is sketched per call
+        self._anon = dataModel if isinstance(dataModel, PlusAnonymousUserDataModel) else None
+        if self._anon is not None:
+            dataModel = self._anon.getDelegate()
         self._model = dataModel
         self._conf = conf
         self._hfb = hfBuilder
@@ -191,9 +274,31 @@ class CosineCM:
     def table(self):
         return self._table
 
+    # ---- the temporary user of a PlusAnonymousUserDataModel ----
+    def _is_temp(self, userID):
+        return self._anon is not None and userID == PlusAnonymousUserDataModel.TEMP_USER_ID
+
+    def _temp_prefs(self):
+        """The temporary preferences (NoSuchUserException when unset)."""
+        return self._anon.getPreferencesFromUser(PlusAnonymousUserDataModel.TEMP_USER_ID)
+
+    def anonymousEstimates(self, theNeighborhood, itemIDs, capper=None):
+        """doEstimatePreference(TEMP_USER_ID, neighbourhood, item) per item."""
+        keys, vals = self._temp_prefs()
+        try:
+            return self._table.anonymous_estimate_preferences(keys, vals, theNeighborhood, itemIDs, capper)
+        except _lib.CmsError as e:
+            raise _map_error(e, "user")
+
     # ---- UserSimilarity ----
     def userSimilarity(self, userID1, userID2):
         try:
+            if self._is_temp(userID1) or self._is_temp(userID2):
+                other = userID2 if self._is_temp(userID1) else userID1
+                if self._is_temp(other):
+                    raise ValueError("userSimilarity of the temporary user with itself")
+                keys, vals = self._temp_prefs()
+                return float(self._table.anonymous_similarities(keys, vals, [other])[0])
             return self._table.similarity(userID1, userID2)
         except _lib.CmsError as e:
             raise _map_error(e, "user")
@@ -230,6 +335,9 @@ class CosineCM:
         if howMany < 1:
             raise ValueError("howMany must be at least 1")
         try:
+            if self._is_temp(userID):
+                ids, _, cnt = self._table.anonymous_most_similar([self._temp_prefs()], howMany)
+                return ids[0, :int(cnt[0])]
             ids, _ = self._table.most_similar(userID, howMany)
         except _lib.CmsError as e:
             raise _map_error(e, "user")
@@ -322,6 +430,8 @@ class GenericUserBasedRecommender:
         """doEstimatePreference for many items at once (one GPU launch)."""
         if len(theNeighborhood) == 0:
             return np.full(len(itemIDs), np.nan, np.float32)
+        if theUserID == PlusAnonymousUserDataModel.TEMP_USER_ID and isinstance(self._model, PlusAnonymousUserDataModel):
+            return self._sim.anonymousEstimates(theNeighborhood, itemIDs, self._capper)
         try:
             return self._sim.table.estimate_preferences(theUserID, theNeighborhood, itemIDs, self._capper)
         except _lib.CmsError as e:
