@@ -165,6 +165,41 @@ int cms_ingest(cms_handle* h, const int64_t* owner, const int64_t* key, const fl
  * input must stay allocated until cms_synchronize (or a blocking call) returns. */
 int cms_ingest_device_rows(cms_handle* h, const int64_t* d_row, const int64_t* d_key, const float* d_val,
                            int64_t n);
+/* DoubleCountMinSketch.update(key, -val) for pairs that WERE ingested: the table of the
+ * remaining stream, counter for counter -- table[owner][i][h_i(key)] -= val * 2^frac_bits
+ * for every sketch row i, and the owner's mass falls by the same amount.  What
+ * FileDataModel's update files state as removed or changed preferences
+ * (FileDataModel.java:493-527), applied to the live table instead of a rebuild.
+ * Owners by ID, host memory.
+ *   Values: val NULL means 1.0 each; duplicate pairs add; a zero value is a no-op; values
+ * are validated exactly as a host ingest validates them (CMS_E_VALUE).  An unknown owner ID
+ * is CMS_E_NO_SUCH_ID.  n == 0 returns CMS_OK and changes nothing; a batch holds fewer than
+ * 2^31 pairs (CMS_E_PARAM).
+ *   States: fixed shape, CMS_COUNTER_U32, no communicator; before or after cms_finalize.
+ * CMS_E_STATE for an fp64 handle ((a + b) - b is not a in fp64), a per-owner handle (it keeps
+ * the DataModel: a new CSR ingest replaces it) and a handle with a communicator (the delta
+ * log is additive).  A pending device-ingest error is reported first, as cms_synchronize would.
+ *   Rules, all checked for the whole batch before the first write: for every owner the
+ * batch's summed decrement is at most its mass; for every counter (owner, sketch row,
+ * bucket) the batch's decrements SUMMED PER COUNTER -- duplicates of a pair, and distinct
+ * keys that share a bucket of that row -- are at most the live counter.  Either violation is
+ * CMS_E_OVERFLOW, the message naming an offending owner; so is any non-zero batch against an
+ * empty handle.  A refused call leaves the handle bit for bit as it was.
+ *   A sketch cannot prove that a pair was ever ingested: the rules are NECESSARY, NOT
+ * SUFFICIENT.  The result is some stream's table only if the batch is a sub-stream of what
+ * was ingested; a batch that merely fits the counters leaves a table no stream built.
+ *   On success pairs_ingested falls by n (saturating at 0) and the handle is "ingested, not
+ * finalized", as after cms_subtract_table: queries return CMS_E_STATE until cms_finalize
+ * re-derives norms and row maxima.  With kept cms_top_k_refresh lists the batch's owners are
+ * marked touched: the next refresh is incremental.  Dense rows keep their form and place
+ * (nothing narrows or returns to the shared zero row); a live list row that loses entries
+ * is rewritten densely first. */
+int cms_retract(cms_handle* h, const int64_t* owner, const int64_t* key, const float* val, int64_t n);
+/* The same for pairs resident on the device, owners by row index (a row outside
+ * [0, num_owners) is CMS_E_PARAM).  BLOCKING and all-or-nothing (unlike
+ * cms_ingest_device_rows): the check's verdict is needed before the first write. */
+int cms_retract_device_rows(cms_handle* h, const int64_t* d_row, const int64_t* d_key, const float* d_val,
+                            int64_t n);
 /* CSR from host memory: the owner at row r has keys[offsets[r] .. offsets[r+1])
  * -- the DataModel layout (one PreferenceArray per owner,
  * GenericUserPreferenceArray.java:52-54).  offsets has num_owners+1 entries. */

@@ -49,6 +49,7 @@ EXPORTS = [
     "cms_checkpoint_info", "cms_merge_table", "cms_merge_table_device", "cms_subtract_table", "cms_subtract_table_device",
     "cms_anonymous_similarities", "cms_anonymous_most_similar", "cms_anonymous_estimate_preferences",
     "cms_anonymous_batch",
+    "cms_retract", "cms_retract_device_rows",
 ]
 
 
@@ -121,6 +122,8 @@ _SIGS = {
     "cms_hash_keys": (_int, [_vp, _vp, _i64, _vp]),
     "cms_ingest": (_int, [_vp, _vp, _vp, _vp, _i64]),
     "cms_ingest_device_rows": (_int, [_vp, _vp, _vp, _vp, _i64]),
+    "cms_retract": (_int, [_vp, _vp, _vp, _vp, _i64]),
+    "cms_retract_device_rows": (_int, [_vp, _vp, _vp, _vp, _i64]),
     "cms_ingest_csr": (_int, [_vp, _vp, _vp, _vp]),
     "cms_ingest_csr_device": (_int, [_vp, _vp, _vp, _vp]),
     "cms_reset": (_int, [_vp]),

@@ -673,6 +673,58 @@ int cms_ingest_device_rows(cms_handle* h, const int64_t* d_row, const int64_t* d
   return rc;
 }
 
+// the handles a retraction is defined on (include/mahout_cms.h)
+static int check_retracts(cms_handle* h, const char* what) {
+  if (h->per_owner)
+    return set_error(CMS_E_STATE, "%s: a per-owner-shape handle keeps the DataModel (a new CSR ingest replaces it)", what);
+  if (h->f64)
+    return set_error(CMS_E_STATE, "%s: fp64 counters do not subtract: (a + b) - b is not a in fp64, so the result would be no stream's table",
+                     what);
+  if (h->comm || h->ext_comm || h->multi() || h->ext_merged)
+    return set_error(CMS_E_STATE, "%s: the handle has a communicator (the delta log of a merged table is additive)", what);
+  return CMS_OK;
+}
+
+int cms_retract(cms_handle* h, const int64_t* owner, const int64_t* key, const float* val, int64_t n) {
+  if (!h || (n > 0 && (!owner || !key))) return set_error(CMS_E_PARAM, "null argument");
+  if (n <= 0) return CMS_OK;
+  if (int rc = cms_synchronize(h)) return rc;  // a pending device-ingest error comes first: nothing is retracted
+  Guard g(h);
+  if (int rc = check_retracts(h, "cms_retract")) return rc;
+  CMS_HIP(h->ws_in_row.ensure(sizeof(int64_t) * n));
+  CMS_HIP(h->ws_in_key.ensure(sizeof(int64_t) * n));
+  if (val) CMS_HIP(h->ws_in_val.ensure(sizeof(float) * n));
+  int64_t* d_row = h->ws_in_row.as<int64_t>();
+  const float* d_val = val ? h->ws_in_val.as<float>() : nullptr;
+  CMS_HIP(hipMemcpyAsync(d_row, owner, sizeof(int64_t) * n, hipMemcpyHostToDevice, h->stream));
+  CMS_HIP(hipMemcpyAsync(h->ws_in_key.ptr, key, sizeof(int64_t) * n, hipMemcpyHostToDevice, h->stream));
+  if (val) CMS_HIP(hipMemcpyAsync(h->ws_in_val.ptr, val, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
+  const bool by_id = !h->h_owner_ids.empty();
+  int rc;
+  if (by_id && (rc = map_owner_ids(h, d_row, n, d_row))) return rc;  // in place, as cms_ingest
+  if ((rc = retract_validate(h, by_id ? nullptr : d_row, d_val, n))) return rc;
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  if ((rc = check_flags(h, by_id))) return rc;
+  if ((rc = retract_coo_device(h, d_row, h->ws_in_key.as<int64_t>(), d_val, n, by_id))) return rc;
+  h->pairs_ingested = h->pairs_ingested > n ? h->pairs_ingested - n : 0;
+  return CMS_OK;
+}
+
+int cms_retract_device_rows(cms_handle* h, const int64_t* d_row, const int64_t* d_key, const float* d_val, int64_t n) {
+  if (!h || (n > 0 && (!d_row || !d_key))) return set_error(CMS_E_PARAM, "null argument");
+  if (n <= 0) return CMS_OK;
+  if (int rc = cms_synchronize(h)) return rc;
+  Guard g(h);
+  if (int rc = check_retracts(h, "cms_retract_device_rows")) return rc;
+  int rc = retract_validate(h, d_row, d_val, n);
+  if (rc) return rc;
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  if ((rc = check_flags(h, false))) return rc;
+  if ((rc = retract_coo_device(h, d_row, d_key, d_val, n, false))) return rc;
+  h->pairs_ingested = h->pairs_ingested > n ? h->pairs_ingested - n : 0;
+  return CMS_OK;
+}
+
 int cms_ingest_csr(cms_handle* h, const int64_t* offsets, const int64_t* keys, const float* vals) {
   if (h && h->ext_merged)
     return set_error(CMS_E_STATE, "table merged through cms_finalize_with: cms_reset starts a new epoch");
@@ -796,7 +848,7 @@ int cms_release_scratch(cms_handle* h) {
                   &h->ws_out, &h->ws_slab, &h->ws_topq, &h->ws_tiles, &h->ws_cand, &h->ws_srow,
                   &h->ws_mbnd, &h->ws_mbits, &h->ws_mwoff, &h->ws_mpacked, &h->rf_ids, &h->rf_sc, &h->rf_cnt,
                   &h->rf_full, &h->rf_touch, &h->rf_new, &h->rf_redo, &h->rf_perm,
-                  &h->an_in, &h->an_sk, &h->an_nz, &h->an_meta, &h->an_rows, &h->an_out};
+                  &h->an_in, &h->an_sk, &h->an_nz, &h->an_meta, &h->an_rows, &h->an_out, &h->ws_retract};
   for (DevBuf* b : ws) b->release();
   // the kept refresh lists and touched marks are gone: the next COO ingest must not mark
   // into rf_touch, and the next cms_top_k_refresh is a whole job

@@ -367,6 +367,9 @@ struct cms_handle {
   // bucket lists [Q][d][w], the per-(profile, row) norms / square roots / list
   // lengths and per-profile maxima, the explicit owner rows, the outputs
   cms::DevBuf an_in, an_sk, an_nz, an_meta, an_rows, an_out;
+  // pair-by-pair retraction (cms_retract.hip): per-owner batch masses, pair
+  // counts and offsets, the run lists and the batch's grouped order
+  cms::DevBuf ws_retract;
 
   // communicator: RCCL (cms_comm_init) or a caller transport (cms_comm_init_transport)
   ncclComm_t comm = nullptr;
@@ -533,6 +536,15 @@ int validate_batch(cms_handle* h, const int64_t* d_rows, const float* d_val, int
 // offsets[0] == 0 and non-decreasing (flags kFlagBadRow otherwise)
 int check_offsets_device(cms_handle* h, const int64_t* d_off);
 int hash_keys_device(cms_handle* h, const int64_t* d_keys, int64_t n, int32_t* d_out);
+// ---- cms_retract.hip ----
+// flags rows outside [0,n) (d_rows null: not checked) and values no ingest would take, as validate_batch does
+int retract_validate(cms_handle* h, const int64_t* d_rows, const float* d_val, int64_t n);
+// a validated COO batch (rows in [0,n)) taken out of the live u32 table, all or
+// nothing: CMS_E_OVERFLOW (naming an owner: its ID when by_id, else its row)
+// when an owner's batch mass exceeds its row mass or a counter's summed
+// decrements exceed it, and then nothing was written.  Blocking.
+int retract_coo_device(cms_handle* h, const int64_t* d_row, const int64_t* d_key, const float* d_val, int64_t n,
+                       bool by_id);
 int scan_exclusive_u32(cms_handle* h, const uint32_t* in, uint32_t* out, int64_t L, uint32_t* bsum);
 // List rows (kFormList) may be stored: forms, the tunable, and a d x w u16
 // image that fits the merge's LDS (k_merge_pack expands them there).

@@ -182,7 +182,13 @@ def java_parse_long(s):
 
 
 class FileDataModel(GenericDataModel):
-    """T/impl/model/file/FileDataModel.java, one data file, no update files:
+    """T/impl/model/file/FileDataModel.java: one data file and, with
+    update_files=True, the reference's update files (:92-101, :239-334) --
+    files beside the data file whose names share its name up to the first
+    period, not older than it, read after it in ascending modification time
+    with the same line rules, so a later line deletes or replaces an earlier
+    preference.  refresh() re-reads everything.  The default reads the data
+    file alone:
 
     - the delimiter is ',' if the first data line (blank and '#' lines
       skipped) holds one, else tab (determineDelimiter, :344-352); every
@@ -199,7 +205,41 @@ class FileDataModel(GenericDataModel):
       (GenericDataModel.toDataMap keeps the emptied collection, :160-168).
     """
 
-    def __init__(self, path, transpose=False):
+    def __init__(self, path, transpose=False, update_files=False):
+        self._path = path
+        self._transpose = transpose
+        self._update_files = update_files
+        self._load()
+
+    def refresh(self, alreadyRefreshed=None):
+        """Refreshable.refresh: re-read the data file (and, with
+        update_files, every update file).  The model's arrays are replaced,
+        never changed in place."""
+        self._load()
+
+    def _find_update_files(self):
+        """findUpdateFilesAfter(dataFile.lastModified()) (:313-334): the plain
+        files of the data file's directory whose names start with the data
+        file's name up to its first period, other than the data file, not
+        older than it -- in ascending modification time (a TreeMap keyed by
+        it: of two files with one time the later listed replaces the other)."""
+        import os
+        name = os.path.basename(self._path)
+        start = name.split(".", 1)[0]
+        parent = os.path.dirname(os.path.abspath(self._path))
+        t0 = os.stat(self._path).st_mtime_ns
+        by_time = {}
+        for fn in sorted(os.listdir(parent)):
+            p = os.path.join(parent, fn)
+            if os.path.isdir(p) or not fn.startswith(start) or fn == name:
+                continue
+            t = os.stat(p).st_mtime_ns
+            if t >= t0:
+                by_time[t] = p
+        return [by_time[t] for t in sorted(by_time)]
+
+    def _load(self):
+        path, transpose = self._path, self._transpose
         with open(path) as f:
             lines = [ln.rstrip("\n").rstrip("\r") for ln in f]
         first = next((ln for ln in lines if ln and ln[0] != "#"), None)
@@ -213,6 +253,10 @@ class FileDataModel(GenericDataModel):
             raise ValueError("Did not find a delimiter in first line")
         ftok = first.split(delim)
         has_values = len(ftok) >= 3 and ftok[2] != ""
+        if self._update_files:  # processed after the data file, with its delimiter and line rules (:260-262)
+            for up in self._find_update_files():
+                with open(up) as f:
+                    lines.extend(ln.rstrip("\n").rstrip("\r") for ln in f)
         prefs = {}
         for line in lines:
             if not line or line[0] == "#":
@@ -237,3 +281,37 @@ class FileDataModel(GenericDataModel):
         super().__init__(prefs)
         if not has_values:
             self.values = None  # GenericBooleanPrefDataModel
+
+
+def preference_delta(old, new):
+    """What turns `old`'s sketches into `new`'s, for two models over the same
+    user IDs: ((users, items, values) to retract, (users, items, values) to
+    ingest) as COO arrays, users by ID.  Retracted are the removed
+    preferences and the changed ones at their OLD values; ingested the added
+    preferences and the changed ones at their NEW values (a boolean model's
+    values count as 1.0).  ValueError when the user IDs differ."""
+    if not np.array_equal(old.user_ids, new.user_ids):
+        raise ValueError("preference_delta: the models differ in their user IDs")
+
+    def coo(m):
+        u = np.repeat(np.asarray(m.user_ids, np.int64), np.diff(m.offsets))
+        v = np.ones(m.keys.size, np.float32) if m.values is None else np.asarray(m.values, np.float32)
+        return u, np.asarray(m.keys, np.int64), v
+
+    uo, ko, vo = coo(old)
+    un, kn, vn = coo(new)
+    u = np.concatenate([uo, un])
+    k = np.concatenate([ko, kn])
+    v = np.concatenate([vo, vn])
+    src = np.concatenate([np.zeros(uo.size, np.int8), np.ones(un.size, np.int8)])
+    order = np.lexsort((src, k, u))  # a preference of both models: old then new, adjacent
+    u, k, v, src = u[order], k[order], v[order], src[order]
+    both = (u[:-1] == u[1:]) & (k[:-1] == k[1:]) & (src[:-1] == 0) & (src[1:] == 1)
+    same = both & (v[:-1] == v[1:])
+    keep_old = np.ones(u.size, bool)  # the old side of an unchanged preference leaves, and its new side
+    keep_new = np.ones(u.size, bool)
+    keep_old[:-1] &= ~same
+    keep_new[1:] &= ~same
+    r = (src == 0) & keep_old
+    a = (src == 1) & keep_new
+    return (u[r], k[r], v[r]), (u[a], k[a], v[a])

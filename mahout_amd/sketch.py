@@ -177,6 +177,29 @@ class SketchTable:
         elif s is None:
             self.synchronize()
 
+    def retract(self, owner, key, val=None):
+        """Take pairs that were ingested out of the live table (cms_retract):
+        DoubleCountMinSketch.update(key, -val) per pair, owners by ID.  All or
+        nothing: CMS_E_OVERFLOW (nothing written) when an owner's batch mass
+        exceeds its mass or a counter's summed decrements exceed it.  The
+        table needs finalize() before the next query."""
+        owner = np.ascontiguousarray(owner, np.int64)
+        key = np.ascontiguousarray(key, np.int64)
+        v = None if val is None else np.ascontiguousarray(val, np.float32)
+        if owner.size != key.size or (v is not None and v.size != key.size):
+            raise ValueError("owner/key/val length mismatch")
+        check(self._lib.cms_retract(self._h, _ptr(owner), _ptr(key), _ptr(v), owner.size))
+
+    def retract_device_rows(self, d_row, d_key, d_val, n):
+        """retract() for pairs resident on the device, owners by row index
+        (cms_retract_device_rows).  Blocking, unlike ingest_device_rows: the
+        library's stream waits for the producers on torch's current stream,
+        and the table has changed (or the call was refused) on return."""
+        s = _torch_stream(d_row, d_key, d_val)
+        if s:
+            check(self._lib.cms_wait_stream(self._h, ctypes.c_void_p(s)))
+        check(self._lib.cms_retract_device_rows(self._h, _dev_ptr(d_row), _dev_ptr(d_key), _dev_ptr(d_val), int(n)))
+
     def ingest_csr(self, offsets, keys, vals=None):
         offsets = np.ascontiguousarray(offsets, np.int64)
         keys = np.ascontiguousarray(keys, np.int64)

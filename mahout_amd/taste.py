@@ -21,7 +21,7 @@ import math
 import numpy as np
 
 from . import _lib
-from .datamodel import NoSuchUserException
+from .datamodel import GenericDataModel, NoSuchUserException, preference_delta
 from .sketch import SketchTable, frac_bits_for, shape_from_delta_epsilon
 
 
@@ -269,6 +269,46 @@ class CosineCM:
             self._table.finalize()
         except _lib.CmsError as e:
             raise _map_error(e)
+        # what the table was built from (the model's arrays are replaced, never
+        # changed in place): refresh() applies the difference to a changed model
+        self._built = None if self._sketches is not None or self._per_owner else (
+            m.user_ids, m.offsets, m.keys, m.values, fb, counters)
+
+    def setDataModel(self, dataModel):
+        """The DataModel the next refresh() reads (the sketches still hold the
+        previous one until then)."""
+        if not dataModel.hasPreferenceValues():
+            raise ValueError("DataModel doesn't have preference values")
+        self._anon = dataModel if isinstance(dataModel, PlusAnonymousUserDataModel) else None
+        self._model = self._anon.getDelegate() if self._anon is not None else dataModel
+
+    def _refresh_in_place(self):
+        """The changed model's difference (datamodel.preference_delta) applied
+        to the live table as retract + ingest + finalize: counter for counter
+        the table a rebuild gives.  False when the table has to be rebuilt:
+        nothing changed since the build, per-owner shapes or fp64 counters, or
+        another user-ID universe or counter unit."""
+        b, m = self._built, self._model
+        if b is None or b[5] != "u32":
+            return False
+        if m.offsets is b[1] and m.keys is b[2] and m.values is b[3]:
+            return False
+        if not np.array_equal(m.user_ids, b[0]):
+            return False
+        fb, counters = counter_units(m.offsets, m.values)
+        if counters != "u32" or fb != b[4]:
+            return False
+        (ru, rk, rv), (au, ak, av) = preference_delta(GenericDataModel.from_csr(b[0], b[1], b[2], b[3]), m)
+        try:
+            if ru.size:
+                self._table.retract(ru, rk, rv)
+            if au.size:
+                self._table.ingest(au, ak, av)
+            self._table.finalize()
+        except _lib.CmsError:
+            return False  # (the rebuild closes this table)
+        self._built = (m.user_ids, m.offsets, m.keys, m.values, fb, counters)
+        return True
 
     @property
     def table(self):
@@ -352,7 +392,13 @@ class CosineCM:
             raise _map_error(e, "user")
 
     def refresh(self, alreadyRefreshed=None):
-        """Refreshable.refresh: rebuild every sketch from the data model."""
+        """Refreshable.refresh: every sketch is the data model's again.  A
+        model that changed since the build (FileDataModel.refresh(), or
+        setDataModel) over the same users is applied in place, its removed and
+        changed preferences retracted and its new ones ingested; otherwise
+        every sketch is rebuilt, as the reference does."""
+        if self._refresh_in_place():
+            return
         self._table.close()
         self._sketches = None  # (a refresh reads the DataModel, as the reference's does)
         self._build()
