@@ -623,6 +623,40 @@ int cms_merge_table_device(cms_handle* h, const void* d_buf, int64_t bytes);
  * row that loses entries is rewritten densely first. */
 int cms_subtract_table(cms_handle* h, const char* path);
 int cms_subtract_table_device(cms_handle* h, const void* d_buf, int64_t bytes);
+/* Compacting: every writer above widens, promotes or moves a row and none
+ * narrows one, so after merges and subtractions a table stores far more than
+ * its counters need.  Re-store every owner row in the narrowest form its
+ * counters need now and lay the table out anew.  *rows_changed (may be NULL) =
+ * owners whose stored form or place class differs afterwards.
+ * The target form of a row with largest counter cmax and mass M, in order:
+ * cmax == 0: no storage (the shared zero row); M >= 2^16 or cmax >= 2^16: u32;
+ * else the narrowest of 1-/2-/4-/8-/16-bit rows the handle stores that holds
+ * cmax -- or a sorted list of M keys where frac_bits == 0, the handle stores
+ * lists, every sketch row sums to M, M <= min(CMS_LIST_KEYS, 1024),
+ * depth * M <= 8192, the list's 2 + 2 * depth * M bytes are strictly fewer
+ * than the dense row's, and cmax <= 255 (no list holds a bucket more than 255
+ * times, as no built list does: the writers re-count list entries in u8).  Place classes are the forms' own and the bounds the
+ * rows' largest counters (0 for u32 rows), as a checkpoint of defaults records.
+ * No counter, row mass, owner ID or hash parameter changes, nor does
+ * pairs_ingested, and the handle's state is carried over: a finalized handle
+ * stays finalized and every query returns the bits it returned before, without
+ * a new cms_finalize; "ingested, not finalized" stays so; kept
+ * cms_top_k_refresh lists and touched marks survive (scores do not depend on
+ * storage).  Without the compact layout (CMS_NO_COMPACT=1) rows keep whole
+ * slots: stored_bytes falls, table_bytes need not.
+ * The handle is fixed-shape, CMS_COUNTER_U32 and without a communicator, before
+ * or after cms_finalize: CMS_E_STATE for an fp64 handle (one form: nothing to
+ * narrow), a per-owner handle and a handle with a communicator.  A pending
+ * device-ingest error is reported first, as cms_synchronize would.  An empty
+ * handle returns CMS_OK and 0.  The call holds the handle exclusively.
+ * Failure: the re-formed rows are packed into a transient buffer of about the
+ * new stored bytes beside the old table and verified there; a state error, a
+ * pending ingest error or CMS_E_OOM for that buffer is returned before the
+ * first change and leaves the handle bit for bit as it was.  If a HIP call
+ * fails after the old rows have been given up, the table is lost: the handle
+ * is left empty and usable, as after cms_reset, and the call returns CMS_E_HIP
+ * with a message that says so. */
+int cms_compact_table(cms_handle* h, int64_t* rows_changed);
 /* The parameters a handle needs to load the file (host only: no device call):
  * depth, width, counter type, seed, num_owners and frac_bits from its header;
  * weighting unweighted, device -1, flags 0.  CMS_E_PARAM for a file that is

@@ -50,6 +50,7 @@ EXPORTS = [
     "cms_anonymous_similarities", "cms_anonymous_most_similar", "cms_anonymous_estimate_preferences",
     "cms_anonymous_batch",
     "cms_retract", "cms_retract_device_rows",
+    "cms_compact_table",
 ]
 
 
@@ -181,6 +182,7 @@ _SIGS = {
     "cms_merge_table_device": (_int, [_vp, _vp, _i64]),
     "cms_subtract_table": (_int, [_vp, ctypes.c_char_p]),
     "cms_subtract_table_device": (_int, [_vp, _vp, _i64]),
+    "cms_compact_table": (_int, [_vp, ctypes.POINTER(_i64)]),
     "cms_checkpoint_info": (_int, [ctypes.c_char_p, ctypes.POINTER(CmsParams), ctypes.POINTER(_i64)]),
     "cms_anonymous_similarities": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "cms_anonymous_most_similar": (_int, [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),

@@ -496,6 +496,65 @@ def diff_counters(minuend, subtrahend):
     return out, a.masses - b.masses
 
 
+def compact_form(cmax, mass, row_sums, depth, width, frac_bits=0, list_keys=256, forms=True):
+    """The form (a ROW_FORMS name) SketchTable.compact re-stores a u32 row in:
+    the numpy twin of ckpt::compact_form (cms_checkpoint.cpp).  cmax: the
+    row's largest counter; mass: its row mass; row_sums: the sums of its
+    `depth` sketch rows (None: not known, which rules a list out); list_keys:
+    the handle's list limit (CMS_LIST_KEYS; 0: no lists); forms: False for a
+    handle that stores only zero / u16 / u32 rows (CMS_NO_FORMS).  In order:
+
+      1. cmax == 0: "zero";
+      2. mass >= 2^16 or cmax >= 2^16: "u32";
+      3. D = the narrowest dense form the handle stores that holds cmax
+         (default_form);
+      4. "list" instead of D only when frac_bits == 0, the handle stores lists,
+         every sketch row sums to the mass m, 1 <= m <= min(list_keys, 1024),
+         depth * m <= 8192, 2 + 2 * depth * m < D's stored bytes, and
+         cmax <= 255: no list holds a bucket more than 255 times, as no built
+         list does (the library's writers re-count list entries in u8
+         counters, so a fuller bucket would wrap at the next write)."""
+    cmax, mass = int(cmax), int(mass)
+    if cmax == 0:
+        return "zero"
+    if mass >= 1 << 16 or cmax >= 1 << 16:
+        return "u32"
+    dense = default_form(cmax, mass, depth, width) if forms else "u16"
+    m = mass
+    if (frac_bits == 0 and forms and list_keys > 0 and cmax <= 255 and shape_has_form("list", depth, width)
+            and row_sums is not None
+            and len(row_sums) == depth and all(int(s) == m for s in row_sums)
+            and 1 <= m <= min(int(list_keys), LIST_MAX_KEYS) and depth * m <= LIST_MAX_ENTRIES
+            and 2 + 2 * depth * m < row_length(_FORM[dense], depth, width)):
+        return "list"
+    return dense
+
+
+def compact_checkpoint(ckpt_or_bytes, list_keys=256, forms=True):
+    """The image (bytes) of the same table with every row in the form
+    compact_form gives it, default place classes and bounds, the image's own
+    masses, owner IDs, hash parameters, seed and pairs_ingested: the no-GPU
+    specification of SketchTable.compact (save_device() after compact() is
+    compact_checkpoint(save_device() before), with the handle's list_keys and
+    forms).  A list row's entries are, per sketch row, the buckets in
+    ascending order, bucket j repeated c[j] times.  u32 tables only."""
+    c = ckpt_or_bytes if isinstance(ckpt_or_bytes, Checkpoint) else Checkpoint(ckpt_or_bytes)
+    if c.counter_type != 0:
+        raise ValueError("fp64 counters are stored in one form: there is nothing to narrow")
+    n, d, w = c.num_owners, c.depth, c.width
+    counters = np.zeros((n, d, w), np.uint64)
+    names, lists = [], {}
+    for r in range(n):
+        x = c.row_counters(r)
+        counters[r] = x
+        name = compact_form(int(x.max()), int(c.masses[r]), x.sum(axis=1), d, w, c.frac_bits, list_keys, forms)
+        if name == "list":
+            lists[r] = np.stack([np.repeat(np.arange(w), x[i].astype(np.int64)) for i in range(d)])
+        names.append(name)
+    return build_checkpoint(counters, c.a, c.b, seed=c.seed, frac_bits=c.frac_bits, owner_ids=c.owner_ids, forms=names,
+                            lists=lists, masses=c.masses, pairs_ingested=c.pairs_ingested)
+
+
 if __name__ == "__main__":
     import sys
     c = read_checkpoint(sys.argv[1])

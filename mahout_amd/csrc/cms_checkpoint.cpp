@@ -198,5 +198,39 @@ uint64_t merge_increment(const DirEntry& e) {
   return e.mass < cap ? e.mass : cap;
 }
 
+// ---- cms_compact_table: the one statement of the target form (the header's
+// comment; mahout_amd.checkpoint.compact_form is its numpy twin) ----
+
+int compact_form(uint32_t cmax, uint64_t mass, const uint64_t* row_sums, int depth, int width, int frac_bits,
+                 int list_keys, bool forms, uint64_t* len) {
+  const int64_t d = depth, w = width, dw = d * w;
+  const bool narrow = forms && w % 32 == 0;
+  int form;
+  if (cmax == 0) {
+    form = kRowZero;
+  } else if (mass >= (uint64_t(1) << 16) || cmax >= (1u << 16)) {
+    form = kRowHot;
+  } else {
+    form = narrow && w % 128 == 0 && cmax <= 1 ? kRowU1
+         : narrow && w % 64 == 0 && cmax <= 3  ? kRowU2
+         : narrow && cmax <= 15                ? kRowU4
+         : narrow && cmax <= 255               ? kRowU8
+                                               : kRowU16;
+    const uint64_t m = mass;
+    const uint64_t limit = (uint64_t)(list_keys < kListMaxKeys ? list_keys : kListMaxKeys);
+    // (cmax <= 255: the writers re-count a list row's entries in u8 counters -- k_widen_rows, k_ckpt_add_lists -- as
+    // the builder's own lists allow them to; a row with a fuller bucket stays dense)
+    bool list = frac_bits == 0 && narrow && 2 * dw <= 80 * 1024 && list_keys > 0 && row_sums != nullptr && cmax <= 255;
+    for (int i = 0; list && i < depth; ++i) list = row_sums[i] == m;
+    if (list && m >= 1 && m <= limit && (uint64_t)d * m <= (uint64_t)kListMaxEntries &&
+        2 + 2 * (uint64_t)d * m < dense_len(form, dw)) {
+      if (len) *len = 2 + 2 * (uint64_t)d * m;
+      return kRowList;
+    }
+  }
+  if (len) *len = dense_len(form, dw);
+  return form;
+}
+
 }  // namespace ckpt
 }  // namespace cms

@@ -113,5 +113,25 @@ uint64_t merge_increment(const DirEntry& e);
 // single counter going below zero: that is the device's check.)
 const char* check_subtract_masses(const Header& hd, const DirEntry* dir, const uint64_t* live_mass, int64_t n);
 
+// ---- compacting a live table (cms_compact_table) ----
+// The narrowest form (kRow*) that holds a u32 table's row as it is now, and
+// *len = its stored bytes.  cmax: the row's largest counter; mass: its row
+// mass; row_sums: the sums of its depth sketch rows (null: not known, which
+// rules a list out).  forms: the handle stores 1- to 8-bit rows and lists
+// where the shape has them (false: CMS_NO_FORMS); list_keys: the handle's list
+// limit (0: it stores no lists).  In order:
+//   1. cmax == 0: kRowZero -- the owner returns to the shared zero row;
+//   2. mass >= 2^16 or cmax >= 2^16: kRowHot;
+//   3. D = the narrowest of u1 (w % 128 == 0), u2 (w % 64 == 0), u4, u8
+//      (w % 32 == 0 and forms) and u16 that holds cmax;
+//   4. kRowList instead of D only when frac_bits == 0, the shape has lists
+//      (forms, w % 32 == 0, 2 d w <= 80 KiB), every sketch row sums to the
+//      mass m, 1 <= m <= min(list_keys, kListMaxKeys), d m <= kListMaxEntries,
+//      2 + 2 d m is strictly less than D's stored bytes, and cmax <= 255: a
+//      list never holds a bucket more than 255 times, as no built list does
+//      (the writers re-count a list's entries in u8 counters).
+int compact_form(uint32_t cmax, uint64_t mass, const uint64_t* row_sums, int depth, int width, int frac_bits,
+                 int list_keys, bool forms, uint64_t* len);
+
 }  // namespace ckpt
 }  // namespace cms

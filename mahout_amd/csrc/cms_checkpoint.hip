@@ -1267,6 +1267,23 @@ int restore_layout(cms_handle* h, Image& im, Expand& ex) {
     CMS_HIP(hipMemcpyAsync(d_caps, caps.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
     if ((rc = row_layout(h, d_caps, d_caps + n))) return rc;
     CMS_HIP(hipMemcpyAsync(off.data(), h->d_off, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    CMS_HIP(hipStreamSynchronize(h->stream));
+    // A place's class is the narrower of the class row_layout derives from its
+    // size and the class its entry records.  For an image a handle saved the
+    // two are equal (the place is no smaller than the recorded class's units
+    // and no larger than the place it was saved from); an image written with
+    // narrower classes -- the forms' own, as cms_compact_table and
+    // build_checkpoint's defaults record them, 0 for a list -- stays as
+    // written, so save -> load -> save reproduces it.  (A narrower class only
+    // moves a row sooner: the place still holds what the class says.)
+    bool differs = false;
+    for (int64_t r = 0; r < n; ++r) {
+      if (off[r] == 0) continue;
+      const int64_t o = (off[r] & ~kCapMask) | std::min<int64_t>(off[r] & kCapMask, (int64_t)im.dir[r].cls);
+      differs |= o != off[r];
+      off[r] = o;
+    }
+    if (differs) CMS_HIP(hipMemcpyAsync(h->d_off, off.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
   } else {  // whole slots at the identity offsets
     for (int64_t r = 0; r < n; ++r) off[r] = (su + r * su) | kCapU16;
   }
@@ -1856,6 +1873,144 @@ int merge_device(cms_handle* h, const void* d_buf, int64_t bytes, bool subtract 
   return subtract ? subtract_resident(h, im, d_payload) : merge_resident(h, im, d_payload);
 }
 
+// ---- compact ----
+
+// Every owner row re-stored in the form ckpt::compact_form gives its counters
+// as they are now (cms_compact.hip).  The scan, the rule, the re-formed
+// payload beside the table and the loader's verify pass over it all leave the
+// live rows alone: whatever can be refused is refused here, with the table as
+// it was.  Then the arena is emptied and the payload restored as a load
+// restores an image (restore_layout: no holes), and the handle's state --
+// finalized or not, its norms, its kept refresh lists -- is put back: none of
+// it depends on how a row is stored.
+// a step before the first change failed: its status (CMS_E_OOM for an
+// allocation, as hip_fail reports it) under the call's own name
+int compact_refused(int rc, int code = 0) {
+  char was[384];
+  std::snprintf(was, sizeof(was), "%s", cms_last_error());
+  return set_error(code ? code : rc, "cms_compact_table: %s; the table is unchanged", was);
+}
+
+int compact_table(cms_handle* h, int64_t* rows_changed) {
+  const int64_t n = h->n;
+  const int depth = h->p.depth;
+  Image old;  // the rows as they are: forms, place classes, bounds and masses (synchronises)
+  int rc = plan_save(h, old);
+  if (rc) return compact_refused(rc);
+  const int L = lists_allowed(h) ? h->tune.list_keys : 0;
+  const uint64_t list_mass_max =
+      L > 0 && h->p.frac_bits == 0 ? (uint64_t)std::min(std::min(L, kListMaxKeys), kListMaxEntries / depth) : 0;
+  DevBuf d_scan, d_tform, d_dst, d_sum, payload;
+  auto oom = [&](hipError_t e, const char* what) -> int {
+    if (e == hipSuccess) return CMS_OK;
+    (void)hipGetLastError();
+    return set_error(CMS_E_OOM, "cms_compact_table: no device memory for %s; the table is unchanged", what);
+  };
+  if ((rc = oom(d_scan.ensure(sizeof(uint2) * (size_t)n), "the row scan"))) return rc;
+  if ((rc = compact_scan(h, list_mass_max, d_scan.as<uint2>()))) return compact_refused(rc);
+  std::vector<uint2> scan((size_t)n);
+  auto readback = [&](void* dst, const void* src, size_t bytes) -> int {
+    CMS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+    CMS_HIP(hipStreamSynchronize(h->stream));
+    return CMS_OK;
+  };
+  if ((rc = readback(scan.data(), d_scan.ptr, sizeof(uint2) * (size_t)n))) return compact_refused(rc);
+
+  Image im;
+  im.hd = old.hd;
+  im.ids = old.ids;
+  im.dir.resize((size_t)n);
+  std::vector<uint8_t> tform((size_t)n);
+  std::vector<uint64_t> dst((size_t)n), sums((size_t)depth);
+  uint64_t at = 0;
+  int64_t changed = 0;
+  for (int64_t r = 0; r < n; ++r) {
+    const DirEntry& was = old.dir[r];
+    const uint64_t* row_sums = nullptr;
+    if (scan[r].y) {  // every sketch row sums to the mass
+      std::fill(sums.begin(), sums.end(), was.mass);
+      row_sums = sums.data();
+    }
+    uint64_t len = 0;
+    const int form = compact_form(scan[r].x, was.mass, row_sums, depth, h->p.width, h->p.frac_bits, L, h->forms_ok, &len);
+    DirEntry& e = im.dir[r];
+    e.form = (uint8_t)form;
+    e.cls = form >= kRowU1 && form <= kRowU16 ? (uint8_t)(form - kRowU1 + kCapU1) : 0;  // the form's own class
+    e.rsv = 0;
+    e.cbound = form == kRowHot ? 0u : scan[r].x;
+    e.len = len;
+    e.mass = was.mass;
+    e.off = at;
+    at += round16(len);
+    tform[r] = e.form;
+    dst[r] = e.off;
+    // as the handle will hold the row: without the compact layout every narrow
+    // row keeps a whole u16 slot, a row of zeros included
+    uint8_t held_form = e.form, held_cls = e.cls;
+    if (!h->compact && form != kRowHot) {
+      held_cls = kCapU16;
+      if (form == kRowZero) held_form = kRowU16;
+    }
+    changed += held_form != was.form || held_cls != was.cls;
+  }
+  im.hd.payload_bytes = at;
+  im.hd.file_bytes = im.hd.payload_off + at;
+  if (const char* why = check_directory(im.hd, im.dir.data(), n))
+    return set_error(CMS_E_STATE, "cms_compact_table: the re-formed directory is inconsistent (%s); the table is unchanged", why);
+
+  if ((rc = oom(payload.ensure((size_t)std::max<uint64_t>(at, 16)), "the re-formed rows"))) return rc;
+  if ((rc = oom(d_tform.ensure((size_t)n), "the row plan"))) return rc;
+  if ((rc = oom(d_dst.ensure(sizeof(uint64_t) * (size_t)n), "the row plan"))) return rc;
+  if ((rc = oom(d_sum.ensure(2 * sizeof(unsigned long long)), "the row plan"))) return rc;
+  auto plan_up = [&]() -> int {
+    CMS_HIP(hipMemcpyAsync(d_tform.ptr, tform.data(), (size_t)n, hipMemcpyHostToDevice, h->stream));
+    CMS_HIP(hipMemcpyAsync(d_dst.ptr, dst.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    CMS_HIP(hipMemsetAsync(d_sum.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
+    return CMS_OK;
+  };
+  if ((rc = plan_up())) return compact_refused(rc);
+  if ((rc = compact_pack(h, d_tform.as<uint8_t>(), d_dst.as<uint64_t>(), payload.as<uint8_t>(), at,
+                         d_sum.as<unsigned long long>())))
+    return compact_refused(rc);
+  unsigned long long sum = 0;
+  if ((rc = readback(&sum, d_sum.ptr, sizeof(sum)))) return compact_refused(rc);
+  im.hd.checksum = sum;
+  Segs sg;
+  DevBuf d_out;
+  // the loader's own pass over what the pack produced: checksum, pad bytes, every list entry.  A failure of the
+  // pass itself keeps its status; a payload that fails it is this call's own fault, not the caller's argument
+  if ((rc = verify_resident(h, im, payload.as<uint8_t>(), sg, d_out)))
+    return compact_refused(rc, rc == CMS_E_PARAM ? CMS_E_STATE : 0);
+
+  // ---- everything that can be refused has been: the old rows are given up ----
+  const bool was_finalized = h->finalized, had_norms = h->norms_valid;
+  unsigned long long res[2] = {0, 0};
+  Expand ex;  // (stays empty: compact_form gives a handle only forms it holds)
+  auto device_part = [&]() -> int {
+    int r = restore_layout(h, im, ex);
+    if (r) return r;
+    build_segs(im, sg);
+    if ((r = sg.upload(h))) return r;
+    CMS_HIP(hipMemsetAsync(d_out.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
+    if ((r = unpack_range(h, sg, 0, at / 16, payload.as<uint8_t>(), d_out.as<unsigned long long>()))) return r;
+    CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+    CMS_HIP(hipStreamSynchronize(h->stream));
+    return CMS_OK;
+  };
+  rc = device_part();
+  if (rc || res[1] || res[0] != im.hd.checksum || !ex.rows.empty()) {
+    (void)hipGetLastError();
+    (void)leave_empty(h);
+    return set_error(CMS_E_HIP, "cms_compact_table: the table was lost while its rows were laid out anew; the handle is empty, as after cms_reset");
+  }
+  h->finalized = was_finalized;
+  h->norms_valid = had_norms;
+  h->mfma_ready = false;  // the operand images are rebuilt when next asked for
+  h->i8blk_ready = false;
+  *rows_changed = changed;
+  return CMS_OK;
+}
+
 }  // namespace
 }  // namespace cms
 
@@ -1938,6 +2093,24 @@ int cms_subtract_table_device(cms_handle* h, const void* d_buf, int64_t bytes) {
   Guard g(h);
   if (int rc = check_subtracts(h, "cms_subtract_table_device")) return rc;
   return merge_device(h, d_buf, bytes, true);
+}
+
+int cms_compact_table(cms_handle* h, int64_t* rows_changed) {
+  if (!h) return set_error(CMS_E_PARAM, "null handle");
+  if (rows_changed) *rows_changed = 0;
+  if (int rc = cms_synchronize(h)) return rc;  // a pending device-ingest error comes first: nothing is re-stored
+  Guard g(h);
+  if (h->per_owner)
+    return set_error(CMS_E_STATE, "cms_compact_table: a per-owner-shape handle keeps the DataModel, not a table");
+  if (h->comm || h->ext_comm || h->multi())
+    return set_error(CMS_E_STATE, "cms_compact_table: the handle has a communicator (the ranks' copies would no longer be stored alike)");
+  if (h->f64)
+    return set_error(CMS_E_STATE, "cms_compact_table: fp64 counters are stored in one form: there is nothing to narrow");
+  if (h->empty) return CMS_OK;  // every owner is on the zero row already
+  int64_t changed = 0;
+  const int rc = compact_table(h, &changed);
+  if (rc == CMS_OK && rows_changed) *rows_changed = changed;
+  return rc;
 }
 
 int cms_checkpoint_info(const char* path, cms_params* out, int64_t* file_bytes) {

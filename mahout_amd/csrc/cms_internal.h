@@ -545,6 +545,14 @@ int retract_validate(cms_handle* h, const int64_t* d_rows, const float* d_val, i
 // decrements exceed it, and then nothing was written.  Blocking.
 int retract_coo_device(cms_handle* h, const int64_t* d_row, const int64_t* d_key, const float* d_val, int64_t n,
                        bool by_id);
+// ---- cms_compact.hip (cms_compact_table; the driver is in cms_checkpoint.hip) ----
+// d_scan[r] = (largest counter of owner row r, 1 when every sketch row sums to
+// the row mass -- asked only of rows whose mass is in [1, list_mass_max])
+int compact_scan(cms_handle* h, uint64_t list_mass_max, uint2* d_scan);
+// every row re-encoded in the form d_tform[r] (ckpt::kRow*) at d_payload +
+// d_dst[r]; the payload is zeroed first and *d_sum += its checksum
+int compact_pack(cms_handle* h, const uint8_t* d_tform, const uint64_t* d_dst, uint8_t* d_payload, uint64_t payload_bytes,
+                 unsigned long long* d_sum);
 int scan_exclusive_u32(cms_handle* h, const uint32_t* in, uint32_t* out, int64_t L, uint32_t* bsum);
 // List rows (kFormList) may be stored: forms, the tunable, and a d x w u16
 // image that fits the merge's LDS (k_merge_pack expands them there).

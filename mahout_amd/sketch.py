@@ -690,6 +690,17 @@ class SketchTable:
         torch.cuda.current_stream(image.device).synchronize()  # its producers are done
         check(self._lib.cms_subtract_table_device(self._h, ctypes.c_void_p(image.data_ptr()), int(image.numel())))
 
+    def compact(self):
+        """Every owner row re-stored in the narrowest form its counters need
+        now, and the table laid out anew (cms_compact_table): what merges and
+        subtractions widened shrinks back.  No counter, mass or query result
+        changes and the handle's state is kept (no finalize() is needed).
+        Returns the number of owners whose stored form or place class changed.
+        checkpoint.compact_checkpoint is the no-GPU specification."""
+        changed = ctypes.c_int64()
+        check(self._lib.cms_compact_table(self._h, ctypes.byref(changed)))
+        return int(changed.value)
+
     @classmethod
     def from_checkpoint(cls, path, device=-1, weighted=False):
         """A new handle of the file's shape (cms_checkpoint_info), loaded from it."""

@@ -413,6 +413,15 @@ class CosineCM:
         except _lib.CmsError as e:
             raise _map_error(e)
 
+    def compactSketches(self):
+        """Every sketch re-stored in the narrowest form its counters need now
+        (SketchTable.compact): what in-place refreshes widened shrinks back.
+        No similarity or estimate changes.  Returns the owners re-stored."""
+        try:
+            return self._table.compact()
+        except _lib.CmsError as e:
+            raise _map_error(e)
+
     def close(self):
         self._table.close()
 
