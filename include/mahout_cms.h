@@ -657,6 +657,44 @@ int cms_subtract_table_device(cms_handle* h, const void* d_buf, int64_t bytes);
  * is left empty and usable, as after cms_reset, and the call returns CMS_E_HIP
  * with a message that says so. */
 int cms_compact_table(cms_handle* h, int64_t* rows_changed);
+/* Folding: the table of the same stream at a narrower width, without the
+ * stream.  The hash is ((a key + b) mod p) mod width and (s mod w) mod w' =
+ * s mod w' for every divisor w' of w, so
+ *   T'[r][i][j'] = sum of T[r][i][j] over j = j' (mod new_width)
+ * is, counter for counter, the table the stream builds at new_width with the
+ * same hash parameters.  The result is an ordinary checkpoint image of width
+ * new_width -- a file, or device memory -- for cms_load_table into a handle of
+ * that width or cms_merge_table / cms_subtract_table into a live one: depth,
+ * counter type, frac_bits, seed, hash parameters, owner IDs, row masses and
+ * pairs_ingested are the source's; every folded row is stored in the form
+ * cms_compact_table's rule gives it at shape (depth, new_width) under the
+ * handle's CMS_LIST_KEYS / CMS_NO_FORMS, with the forms' own place classes and
+ * the folded largest counters as bounds (0 for u32 rows); a list row's entries
+ * are its buckets ascending, bucket j' repeated T'[r][i][j'] times.
+ * new_width: 1 <= new_width <= width and width % new_width == 0, CMS_E_PARAM
+ * otherwise; new_width == width yields the image of the compacted table.
+ * Accepted exactly where cms_save_table is (fixed shape, before or after
+ * cms_finalize, a multi-rank handle under the save's rule), and u32 counters
+ * only: an fp64 handle returns CMS_E_STATE (a folded fp64 sum is not the
+ * sequential chain in ingest order, so it would be no stream's table).  A
+ * pending device-ingest error is reported first, as cms_synchronize would.
+ * The call holds the handle exclusively and only reads it: no counter, form,
+ * place, mass, norm, kept cms_top_k_refresh list, touched mark, pairs_ingested
+ * or finalized state changes.  A folded counter that would reach 2^32 (only a
+ * loaded image can hold one: a stream's sketch rows sum to a mass below 2^32)
+ * returns CMS_E_OVERFLOW naming the owner row, and nothing is written.  The
+ * table is never expanded: two passes read every stored row once each.
+ * The reference has no counterpart. */
+/* Bytes cms_fold_table would write / cms_fold_table_device needs (runs the
+ * scan: the size depends on each folded row's form). */
+int cms_fold_size(cms_handle* h, int32_t new_width, int64_t* bytes);
+/* The folded image to path: written as path + ".tmp", then renamed. */
+int cms_fold_table(cms_handle* h, int32_t new_width, const char* path);
+/* The folded image into device memory on the handle's GPU (16-byte aligned).
+ * *bytes = the image's length, set whenever the fold itself is accepted;
+ * CMS_E_PARAM when capacity is smaller, and then the buffer is untouched.
+ * Blocking: the image is complete when the call returns. */
+int cms_fold_table_device(cms_handle* h, int32_t new_width, void* d_buf, int64_t capacity, int64_t* bytes);
 /* The parameters a handle needs to load the file (host only: no device call):
  * depth, width, counter type, seed, num_owners and frac_bits from its header;
  * weighting unweighted, device -1, flags 0.  CMS_E_PARAM for a file that is

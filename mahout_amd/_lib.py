@@ -51,6 +51,7 @@ EXPORTS = [
     "cms_anonymous_batch",
     "cms_retract", "cms_retract_device_rows",
     "cms_compact_table",
+    "cms_fold_size", "cms_fold_table", "cms_fold_table_device",
 ]
 
 
@@ -183,6 +184,9 @@ _SIGS = {
     "cms_subtract_table": (_int, [_vp, ctypes.c_char_p]),
     "cms_subtract_table_device": (_int, [_vp, _vp, _i64]),
     "cms_compact_table": (_int, [_vp, ctypes.POINTER(_i64)]),
+    "cms_fold_size": (_int, [_vp, _i32, ctypes.POINTER(_i64)]),
+    "cms_fold_table": (_int, [_vp, _i32, ctypes.c_char_p]),
+    "cms_fold_table_device": (_int, [_vp, _i32, _vp, _i64, ctypes.POINTER(_i64)]),
     "cms_checkpoint_info": (_int, [ctypes.c_char_p, ctypes.POINTER(CmsParams), ctypes.POINTER(_i64)]),
     "cms_anonymous_similarities": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "cms_anonymous_most_similar": (_int, [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),

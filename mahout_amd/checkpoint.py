@@ -555,6 +555,45 @@ def compact_checkpoint(ckpt_or_bytes, list_keys=256, forms=True):
                             lists=lists, masses=c.masses, pairs_ingested=c.pairs_ingested)
 
 
+def fold_checkpoint(ckpt_or_bytes, width, list_keys=256, forms=True):
+    """The image (bytes) of the same stream's table at the narrower width
+    `width`, a divisor of the image's: the no-GPU specification of
+    SketchTable.fold_device.  The hash is ((a key + b) mod p)
+    mod w and (s mod w) mod w' = s mod w' for every divisor w' of w, so
+
+        T'[r][i][j'] = sum of T[r][i][j] over j = j' (mod w')
+
+    is, counter for counter, the table the stream builds at width w' with the
+    same hash parameters.  Every folded row is stored in the form compact_form
+    gives it at shape (depth, width), with default place classes and bounds, as
+    compact_checkpoint stores them; masses, owner IDs, hash parameters, seed,
+    frac_bits and pairs_ingested are the image's own.  fold_checkpoint(img, w)
+    at the image's own width is compact_checkpoint(img).  ValueError for a
+    width that does not divide the image's, for an fp64 image (a folded fp64
+    sum is not the reference's sequential chain in ingest order: no stream's
+    table) and for a folded counter of 2^32 or more."""
+    c = ckpt_or_bytes if isinstance(ckpt_or_bytes, Checkpoint) else Checkpoint(ckpt_or_bytes)
+    if c.counter_type != 0:
+        raise ValueError("fp64 counters do not fold: the folded sum would be no stream's table")
+    n, d, w = c.num_owners, c.depth, c.width
+    width = int(width)
+    if not 1 <= width <= w or w % width:
+        raise ValueError("width %d does not divide the image's width %d" % (width, w))
+    counters = np.zeros((n, d, width), np.uint64)
+    names, lists = [], {}
+    for r in range(n):
+        x = c.row_counters(r).reshape(d, w // width, width).sum(axis=1, dtype=np.uint64)  # (at most 2^15 u32 terms)
+        if int(x.max()) >= 1 << 32:
+            raise ValueError("row %d: a folded counter reaches 2^32" % r)
+        counters[r] = x
+        name = compact_form(int(x.max()), int(c.masses[r]), x.sum(axis=1), d, width, c.frac_bits, list_keys, forms)
+        if name == "list":
+            lists[r] = np.stack([np.repeat(np.arange(width), x[i].astype(np.int64)) for i in range(d)])
+        names.append(name)
+    return build_checkpoint(counters, c.a, c.b, seed=c.seed, frac_bits=c.frac_bits, owner_ids=c.owner_ids, forms=names,
+                            lists=lists, masses=c.masses, pairs_ingested=c.pairs_ingested)
+
+
 if __name__ == "__main__":
     import sys
     c = read_checkpoint(sys.argv[1])

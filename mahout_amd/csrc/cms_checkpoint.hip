@@ -2011,6 +2011,193 @@ int compact_table(cms_handle* h, int64_t* rows_changed) {
   return CMS_OK;
 }
 
+// ---- fold: the table at a width that divides its own, as an image (cms_fold_table) ----
+//
+// Compaction's route without the restore: scan the rows as they fold, give
+// every folded row compact_form's form at shape (depth, wf) and its place in
+// the payload on the host, pack.  The live table is only read.  At wf == width
+// nothing folds and the scan and the pack are the compaction's own.
+struct FoldPlan {
+  Image im;  // header, IDs and directory of the folded image (its checksum after the pack)
+  std::vector<uint8_t> tform;
+  std::vector<uint64_t> dst;
+};
+
+int check_fold_width(cms_handle* h, int32_t wf) {
+  if (wf < 1 || wf > h->p.width || h->p.width % wf != 0)
+    return set_error(CMS_E_PARAM, "cms_fold_table: new_width %d is no divisor of the table's width %d", (int)wf,
+                     (int)h->p.width);
+  return CMS_OK;
+}
+
+int fold_plan(cms_handle* h, int32_t wf, FoldPlan& fp) {
+  const int64_t n = h->n;
+  const int depth = h->p.depth;
+  Image old;  // the source's header, IDs and masses (synchronises)
+  int rc = plan_save(h, old);
+  if (rc) return rc;
+  const bool forms = h->tune.forms;
+  const int L = forms ? h->tune.list_keys : 0;
+  const uint64_t list_mass_max =
+      L > 0 && h->p.frac_bits == 0 ? (uint64_t)std::min(std::min(L, kListMaxKeys), kListMaxEntries / depth) : 0;
+  std::vector<uint2> scan((size_t)n, make_uint2(0u, 0u));
+  if (!h->empty) {  // (an empty handle's rows are all zero: its arrays are stale)
+    DevBuf d_scan;
+    CMS_HIP(d_scan.ensure(sizeof(uint2) * (size_t)n));
+    rc = wf == h->p.width ? compact_scan(h, list_mass_max, d_scan.as<uint2>())
+                          : fold_scan(h, wf, list_mass_max, d_scan.as<uint2>());
+    if (rc) return rc;
+    CMS_HIP(hipMemcpyAsync(scan.data(), d_scan.ptr, sizeof(uint2) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    CMS_HIP(hipStreamSynchronize(h->stream));
+  }
+  for (int64_t r = 0; r < n; ++r)
+    if (scan[r].y & 2u)
+      return set_error(CMS_E_OVERFLOW, "cms_fold_table: owner row %lld: a counter folded to width %d reaches 2^32; nothing is written",
+                       (long long)r, (int)wf);
+  Image& im = fp.im;
+  im.hd = old.hd;
+  im.hd.width = wf;
+  im.ids = old.ids;
+  im.dir.resize((size_t)n);
+  fp.tform.resize((size_t)n);
+  fp.dst.resize((size_t)n);
+  std::vector<uint64_t> sums((size_t)depth);
+  uint64_t at = 0;
+  for (int64_t r = 0; r < n; ++r) {
+    const uint64_t mass = old.dir[r].mass;
+    const uint64_t* row_sums = nullptr;
+    if (scan[r].y & 1u) {  // every sketch row sums to the mass
+      std::fill(sums.begin(), sums.end(), mass);
+      row_sums = sums.data();
+    }
+    uint64_t len = 0;
+    const int form = compact_form(scan[r].x, mass, row_sums, depth, wf, h->p.frac_bits, L, forms, &len);
+    DirEntry& e = im.dir[r];
+    e.form = (uint8_t)form;
+    e.cls = form >= kRowU1 && form <= kRowU16 ? (uint8_t)(form - kRowU1 + kCapU1) : 0;  // the form's own class
+    e.rsv = 0;
+    e.cbound = form == kRowHot ? 0u : scan[r].x;
+    e.len = len;
+    e.mass = mass;
+    e.off = at;
+    at += round16(len);
+    fp.tform[r] = e.form;
+    fp.dst[r] = e.off;
+  }
+  im.hd.payload_bytes = at;
+  im.hd.file_bytes = im.hd.payload_off + at;
+  im.hd.checksum = 0;
+  if (const char* why = check_directory(im.hd, im.dir.data(), n))
+    return set_error(CMS_E_STATE, "cms_fold_table: the folded directory is inconsistent (%s)", why);
+  return CMS_OK;
+}
+
+// the folded rows into d_payload (payload_bytes of the plan, 16-byte aligned); the plan's header gets the checksum
+int fold_payload(cms_handle* h, int32_t wf, FoldPlan& fp, uint8_t* d_payload) {
+  const int64_t n = h->n;
+  const uint64_t at = fp.im.hd.payload_bytes;
+  if (at == 0) return CMS_OK;  // every row is zero
+  DevBuf d_tform, d_dst, d_sum;
+  CMS_HIP(d_tform.ensure((size_t)n));
+  CMS_HIP(d_dst.ensure(sizeof(uint64_t) * (size_t)n));
+  CMS_HIP(d_sum.ensure(2 * sizeof(unsigned long long)));
+  CMS_HIP(hipMemcpyAsync(d_tform.ptr, fp.tform.data(), (size_t)n, hipMemcpyHostToDevice, h->stream));
+  CMS_HIP(hipMemcpyAsync(d_dst.ptr, fp.dst.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  CMS_HIP(hipMemsetAsync(d_sum.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
+  const int rc = wf == h->p.width
+                     ? compact_pack(h, d_tform.as<uint8_t>(), d_dst.as<uint64_t>(), d_payload, at, d_sum.as<unsigned long long>())
+                     : fold_pack(h, wf, d_tform.as<uint8_t>(), d_dst.as<uint64_t>(), d_payload, at, d_sum.as<unsigned long long>());
+  if (rc) return rc;
+  unsigned long long sum = 0;
+  CMS_HIP(hipMemcpyAsync(&sum, d_sum.ptr, sizeof(sum), hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  fp.im.hd.checksum = sum;
+  return CMS_OK;
+}
+
+// header, IDs (and the gap before the directory), directory: the image's first payload_off bytes
+std::vector<uint8_t> image_head(const Image& im) {
+  const Header& hd = im.hd;
+  std::vector<uint8_t> head((size_t)hd.payload_off, 0);
+  std::memcpy(head.data(), &hd, sizeof(hd));
+  if (!im.ids.empty()) std::memcpy(head.data() + hd.ids_off, im.ids.data(), (size_t)hd.ids_bytes);
+  std::memcpy(head.data() + hd.dir_off, im.dir.data(), (size_t)hd.dir_bytes);
+  return head;
+}
+
+int fold_device(cms_handle* h, int32_t wf, void* d_buf, int64_t capacity, int64_t* bytes) {
+  FoldPlan fp;
+  int rc = fold_plan(h, wf, fp);
+  if (rc) return rc;
+  const Header& hd = fp.im.hd;
+  *bytes = (int64_t)hd.file_bytes;
+  if (!d_buf) return CMS_OK;  // (the size only)
+  if (capacity < 0 || (uint64_t)capacity < hd.file_bytes)
+    return set_error(CMS_E_PARAM, "folded device image needs %lld bytes, the buffer has %lld", (long long)hd.file_bytes,
+                     (long long)capacity);
+  if (reinterpret_cast<uintptr_t>(d_buf) & 15) return set_error(CMS_E_PARAM, "device image must be 16-byte aligned");
+  uint8_t* base = static_cast<uint8_t*>(d_buf);
+  if ((rc = fold_payload(h, wf, fp, base + hd.payload_off))) return rc;
+  const std::vector<uint8_t> head = image_head(fp.im);
+  CMS_HIP(hipMemcpyAsync(base, head.data(), head.size(), hipMemcpyHostToDevice, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  return CMS_OK;
+}
+
+int fold_file(cms_handle* h, int32_t wf, const char* path) {
+  FoldPlan fp;
+  int rc = fold_plan(h, wf, fp);
+  if (rc) return rc;
+  const Header& hd = fp.im.hd;
+  // the folded payload is packed whole beside the table (it is smaller than the table's stored bytes), then leaves
+  // through the save path's pinned staging buffers
+  DevBuf payload;
+  if (payload.ensure((size_t)std::max<uint64_t>(hd.payload_bytes, 16)) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_error(CMS_E_OOM, "cms_fold_table: no device memory for the folded rows; nothing is written");
+  }
+  if ((rc = fold_payload(h, wf, fp, payload.as<uint8_t>()))) return rc;
+  const std::string tmp = std::string(path) + ".tmp";
+  TmpRemover cleanup{tmp};  // (declared before the file: it is closed first)
+  File out;
+  out.f = std::fopen(tmp.c_str(), "wb");
+  if (!out.f) return set_error(CMS_E_PARAM, "cannot open %s for writing", tmp.c_str());
+  const auto t_io = std::chrono::steady_clock::now();
+  const std::vector<uint8_t> head = image_head(fp.im);
+  bool ok = std::fwrite(head.data(), 1, head.size(), out.f) == head.size();
+  const uint64_t total = hd.payload_bytes, nchunks = (total + kIoChunk - 1) / kIoChunk;
+  if (ok && nchunks > 0) {
+    Staging st;
+    if ((rc = st.init(std::min(kIoChunk, total), false))) return rc;
+    auto span = [&](uint64_t i) { return std::min(total, (i + 1) * kIoChunk) - i * kIoChunk; };
+    for (uint64_t i = 0; i <= nchunks && ok; ++i) {  // D2H of chunk i while the host writes chunk i - 1
+      if (i < nchunks) {
+        CMS_HIP(hipMemcpyAsync(st.pin[i & 1], payload.as<uint8_t>() + i * kIoChunk, (size_t)span(i), hipMemcpyDeviceToHost,
+                               h->stream));
+        CMS_HIP(hipEventRecord(st.ev_a[i & 1], h->stream));
+      }
+      if (i >= 1) {
+        CMS_HIP(hipEventSynchronize(st.ev_a[(i - 1) & 1]));
+        ok = std::fwrite(st.pin[(i - 1) & 1], 1, (size_t)span(i - 1), out.f) == span(i - 1);
+      }
+    }
+  }
+  const bool closed = std::fclose(out.f) == 0;
+  out.f = nullptr;
+  add_host_time(h, "ckpt_io", t_io);
+  if (!ok || !closed) return set_error(CMS_E_PARAM, "short write to %s", tmp.c_str());
+  if (std::rename(tmp.c_str(), path) != 0) return set_error(CMS_E_PARAM, "cannot rename %s to %s", tmp.c_str(), path);
+  return CMS_OK;
+}
+
+// what a fold accepts: what a save accepts, of u32 counters
+int check_folds(cms_handle* h, int32_t wf) {
+  if (int rc = check_saveable(h, "cms_fold_table")) return rc;
+  if (h->f64)
+    return set_error(CMS_E_STATE, "cms_fold_table: fp64 counters do not fold: a folded sum is not the sequential fp64 chain in ingest order, so the result would be no stream's table");
+  return check_fold_width(h, wf);
+}
+
 }  // namespace
 }  // namespace cms
 
@@ -2111,6 +2298,31 @@ int cms_compact_table(cms_handle* h, int64_t* rows_changed) {
   const int rc = compact_table(h, &changed);
   if (rc == CMS_OK && rows_changed) *rows_changed = changed;
   return rc;
+}
+
+int cms_fold_size(cms_handle* h, int32_t new_width, int64_t* bytes) {
+  if (!h || !bytes) return set_error(CMS_E_PARAM, "null argument");
+  if (int rc = cms_synchronize(h)) return rc;  // a pending device-ingest error comes first
+  Guard g(h);
+  if (int rc = check_folds(h, new_width)) return rc;
+  return fold_device(h, new_width, nullptr, 0, bytes);
+}
+
+int cms_fold_table(cms_handle* h, int32_t new_width, const char* path) {
+  if (!h || !path) return set_error(CMS_E_PARAM, "null argument");
+  if (int rc = cms_synchronize(h)) return rc;  // a pending device-ingest error comes first: nothing is written
+  Guard g(h);
+  if (int rc = check_folds(h, new_width)) return rc;
+  return fold_file(h, new_width, path);
+}
+
+int cms_fold_table_device(cms_handle* h, int32_t new_width, void* d_buf, int64_t capacity, int64_t* bytes) {
+  if (!h || !d_buf || !bytes) return set_error(CMS_E_PARAM, "null argument");
+  *bytes = 0;
+  if (int rc = cms_synchronize(h)) return rc;
+  Guard g(h);
+  if (int rc = check_folds(h, new_width)) return rc;
+  return fold_device(h, new_width, d_buf, capacity, bytes);
 }
 
 int cms_checkpoint_info(const char* path, cms_params* out, int64_t* file_bytes) {

@@ -553,6 +553,17 @@ int compact_scan(cms_handle* h, uint64_t list_mass_max, uint2* d_scan);
 // d_dst[r]; the payload is zeroed first and *d_sum += its checksum
 int compact_pack(cms_handle* h, const uint8_t* d_tform, const uint64_t* d_dst, uint8_t* d_payload, uint64_t payload_bytes,
                  unsigned long long* d_sum);
+// ---- cms_fold.hip (cms_fold_table; the driver is in cms_checkpoint.hip) ----
+// wf divides the handle's width and is at most half of it (wf == width is the
+// compaction's scan and pack).  d_scan[r] = (largest counter of owner row r
+// folded to width wf, saturated at 2^32 - 1; bit 0: every sketch row sums to
+// the row mass, asked as compact_scan asks it; bit 1: a folded counter reached
+// 2^32)
+int fold_scan(cms_handle* h, int32_t wf, uint64_t list_mass_max, uint2* d_scan);
+// every row folded to width wf and encoded in the form d_tform[r] (ckpt::kRow*)
+// at d_payload + d_dst[r]; the payload is zeroed first and *d_sum += its checksum
+int fold_pack(cms_handle* h, int32_t wf, const uint8_t* d_tform, const uint64_t* d_dst, uint8_t* d_payload,
+              uint64_t payload_bytes, unsigned long long* d_sum);
 int scan_exclusive_u32(cms_handle* h, const uint32_t* in, uint32_t* out, int64_t L, uint32_t* bsum);
 // List rows (kFormList) may be stored: forms, the tunable, and a d x w u16
 // image that fits the merge's LDS (k_merge_pack expands them there).

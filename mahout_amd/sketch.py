@@ -103,6 +103,8 @@ class SketchTable:
         self.depth = depth
         self.width = width
         self.seed = seed
+        self.weighted = bool(weighted)
+        self.frac_bits = frac_bits
         self.hash_rows = 32 if per_owner else depth  # CMS_MAX_DEPTH rows for per-owner handles
         if owner_ids is not None:
             self.set_owner_ids(owner_ids)
@@ -700,6 +702,53 @@ class SketchTable:
         changed = ctypes.c_int64()
         check(self._lib.cms_compact_table(self._h, ctypes.byref(changed)))
         return int(changed.value)
+
+    def fold_size(self, width):
+        """Bytes save_folded() would write / fold_device() returns (cms_fold_size)."""
+        b = ctypes.c_int64()
+        check(self._lib.cms_fold_size(self._h, int(width), ctypes.byref(b)))
+        return int(b.value)
+
+    def fold_device(self, width):
+        """The checkpoint image of this table folded to `width`, a divisor of
+        its own, as a torch uint8 tensor on the handle's device
+        (cms_fold_table_device): counter j of every sketch row added into
+        counter j mod width, which is the table the same stream builds at that
+        width with the same hash parameters.  This handle is only read.  The
+        image loads into a handle of the new width and merges into or subtracts
+        from a live one; checkpoint.fold_checkpoint is the no-GPU
+        specification.  u32 counters only."""
+        import torch
+        size = self.fold_size(width)
+        out = torch.empty(size, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(out.device).synchronize()  # (the allocation is the tensor's alone)
+        b = ctypes.c_int64()
+        check(self._lib.cms_fold_table_device(self._h, int(width), ctypes.c_void_p(out.data_ptr()), size, ctypes.byref(b)))
+        return out[:b.value]
+
+    def save_folded(self, path, width):
+        """fold_device(width) written to a checkpoint file (cms_fold_table;
+        written as path + ".tmp", then renamed)."""
+        check(self._lib.cms_fold_table(self._h, int(width), os.fsencode(path)))
+
+    def folded(self, width, device=None, weighted=None):
+        """A new SketchTable of width `width` holding this table folded to it
+        (fold_device, then load_device), on this handle's device and with its
+        weighting unless given.  Not finalized, as after from_checkpoint."""
+        import torch
+        image = self.fold_device(width)
+        device = self.device if device is None else int(device)
+        if device != self.device:
+            image = image.to(torch.device("cuda", device))
+        t = SketchTable(self.num_owners, depth=self.depth, width=int(width), seed=self.seed,
+                        weighted=self.weighted if weighted is None else weighted, device=device,
+                        frac_bits=self.frac_bits, counters=self.counters)
+        try:
+            t.load_device(image)
+        except Exception:
+            t.close()
+            raise
+        return t
 
     @classmethod
     def from_checkpoint(cls, path, device=-1, weighted=False):
