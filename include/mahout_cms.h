@@ -121,7 +121,9 @@ int cms_shape_from_delta_epsilon(double delta, double epsilon, int32_t* width, i
  *   CMS_LIST_KEYS=<n>     ... of <= n keys, unit increments: sparse list rows (256; 0 = none)
  *   CMS_NO_HOT_ROUTING=1  the COO partition sends every owner through both passes
  *   CMS_NO_FP4=1          no e2m1 operand image: every single-limb pair on int8 MFMA
- *   CMS_NO_MLS=1          multi-limb slabs on the 128-row tile kernel instead of k_cosine_mls */
+ *   CMS_NO_MLS=1          multi-limb slabs on the 128-row tile kernel instead of k_cosine_mls
+ *   CMS_THRESHOLD_SLAB_ROWS=<rows>  query rows per slab of cms_threshold_neighbors, rounded up to
+ *                         whole 128-row tiles (default: the top-k's slab budget) */
 int cms_create(const cms_params* p, cms_handle** out);
 void cms_destroy(cms_handle* h);
 const char* cms_last_error(void);
@@ -335,6 +337,52 @@ int cms_most_similar(cms_handle* h, int64_t id, int32_t k, int64_t* out_ids, dou
  * all-pairs top-k pass (config 4).  ids/scores are [row_count][k]; counts[row_count]. */
 int cms_top_k_rows(cms_handle* h, int64_t row_begin, int64_t row_count, int32_t k, int64_t* ids,
                    double* scores, int32_t* counts);
+/* ThresholdUserNeighborhood.getUserNeighborhood(id) for nq owners at once
+ * (T/impl/neighborhood/ThresholdUserNeighborhood.java:77-97): every OTHER
+ * owner whose similarity s = userSimilarity(id, other) -- the value
+ * cms_similarities returns, after normalizeWeightResult -- passes
+ * !Double.isNaN(s) && s >= threshold (:88-90), as one CSR: the list of ids[q]
+ * is out_ids / out_scores [offsets[q], offsets[q + 1]).  The sampling rate is
+ * 1: every owner is considered (SamplingLongPrimitiveIterator's random
+ * sampling is not reproduced).  On a per-owner-shape handle the similarity is
+ * the asymmetric userSimilarity(id, other): the query's preferences at the
+ * other's shape (CosineCM.java:83-96), so v may be in u's list and u not in v's.
+ *
+ * order: CMS_NEIGHBOR_ORDER_ID lists ascending owner ID, the getUserIDs()
+ * order in which the reference adds the neighbours (:86-92);
+ * CMS_NEIGHBOR_ORDER_FASTIDSET lists what it returns, neighborhood.toArray()
+ * of a new FastIDSet() after those adds (:81, :96; FastIDSet.java:157-166),
+ * scores travelling with their IDs.  ids may repeat and come in any order;
+ * each entry gets its own list.
+ *
+ * Capacity protocol: offsets [nq + 1] and *total are complete on every
+ * accepted call, whether or not the lists fit.  out_ids == NULL (capacity 0)
+ * only counts.  With out_ids != NULL and *total > capacity the call returns
+ * CMS_E_PARAM (as cms_save_table_device does for a short buffer) and the
+ * contents of out_ids / out_scores are unspecified: call again with *total.
+ * out_scores may be NULL.  nq == 0 writes offsets[0] = 0, *total = 0.
+ *
+ * CMS_E_STATE before cms_finalize; CMS_E_PARAM for a NaN threshold (the
+ * constructor's checkArgument, :73; any other double is taken, infinities
+ * included), a bad order or a null offsets / total; CMS_E_NO_SUCH_ID for an
+ * unknown ID, before any device work; CMS_E_SKETCH on a per-owner handle with
+ * an owner whose (delta, epsilon) raise CMException; CMS_E_OOM when a chunk's
+ * staging buffer cannot be had.  The call changes nothing in the table; a
+ * merged multi-rank handle answers locally, with no collective. */
+#define CMS_NEIGHBOR_ORDER_ID 0        /* ascending owner ID: the order the reference adds them */
+#define CMS_NEIGHBOR_ORDER_FASTIDSET 1 /* FastIDSet.toArray() of new FastIDSet() after those adds:
+                                          what getUserNeighborhood returns, and the order
+                                          doEstimatePreference sums in */
+int cms_threshold_neighbors(cms_handle* h, const int64_t* ids, int64_t nq, double threshold, int32_t order,
+                            int64_t* offsets /* nq + 1 */, int64_t* out_ids, double* out_scores /* may be NULL */,
+                            int64_t capacity, int64_t* total);
+/* Host only, no handle: out = toArray() of a new FastIDSet() after
+ * add(ids[0..n)) in order (FastIDSet.java:125-166; default size 2, load factor
+ * 1.5); *count <= n (a repeated ID is added once).  An ID equal to FastIDSet's
+ * NULL or REMOVED sentinel (Long.MIN_VALUE, Long.MAX_VALUE) is CMS_E_PARAM,
+ * add's checkArgument (:126).  The implementation is the one
+ * cms_recommend_batch orders getAllOtherItems with. */
+int cms_fastidset_to_array(const int64_t* ids, int64_t n, int64_t* out, int64_t* count);
 /* mostSimilar for EVERY owner (config 4, the suggested cms_topk_all of the
  * scope table): the same lists as cms_top_k_rows(h, 0, num_owners, ...), but
  * each unordered pair's similarity is computed once and streamed into both

@@ -31,6 +31,8 @@ CMS_FORMAT_SPARK_ITEMSIMILARITY = 2
 CMS_UNWEIGHTED = 0
 CMS_WEIGHTED = 1
 CMS_FLAG_COLLECTIVE_SINGLE_RANK = 0x1
+CMS_NEIGHBOR_ORDER_ID = 0
+CMS_NEIGHBOR_ORDER_FASTIDSET = 1
 
 # Every symbol the header declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -52,6 +54,7 @@ EXPORTS = [
     "cms_retract", "cms_retract_device_rows",
     "cms_compact_table",
     "cms_fold_size", "cms_fold_table", "cms_fold_table_device",
+    "cms_threshold_neighbors", "cms_fastidset_to_array",
 ]
 
 
@@ -193,6 +196,8 @@ _SIGS = {
     "cms_anonymous_estimate_preferences": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, ctypes.c_float,
                                                   ctypes.c_float, _vp]),
     "cms_anonymous_batch": (_int, [_vp, _i32, ctypes.POINTER(_i32)]),
+    "cms_threshold_neighbors": (_int, [_vp, _vp, _i64, _dbl, _i32, _vp, _vp, _vp, _i64, ctypes.POINTER(_i64)]),
+    "cms_fastidset_to_array": (_int, [_vp, _i64, _vp, ctypes.POINTER(_i64)]),
 }
 
 _lib = None

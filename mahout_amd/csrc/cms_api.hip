@@ -356,6 +356,8 @@ static int create_impl(const cms_params* p, bool per_owner, cms_handle** out) {
     h->tune.hot_routing = !flag("CMS_NO_HOT_ROUTING");
     h->tune.fp4 = !flag("CMS_NO_FP4");
     h->tune.mls = !flag("CMS_NO_MLS");
+    if (const int rows = num("CMS_THRESHOLD_SLAB_ROWS", 0); rows > 0)  // whole 128-row tiles, at least one
+      h->tune.threshold_slab_rows = std::max<int64_t>(128, ((int64_t)rows + 127) / 128 * 128);
   }
   h->per_owner = per_owner;
   h->f64 = f64;
@@ -1354,6 +1356,54 @@ int cms_top_k_rows(cms_handle* h, int64_t row_begin, int64_t row_count, int32_t 
   if (row_begin < 0 || row_count < 0 || row_begin + row_count > h->n) return set_error(CMS_E_PARAM, "row range");
   if (row_count == 0) return CMS_OK;
   return top_k_host(h, row_begin, row_count, k, ids, scores, counts);
+}
+
+int cms_threshold_neighbors(cms_handle* h, const int64_t* ids, int64_t nq, double threshold, int32_t order,
+                            int64_t* offsets, int64_t* out_ids, double* out_scores, int64_t capacity, int64_t* total) {
+  if (!h || nq < 0 || (nq > 0 && !ids) || !offsets || !total || capacity < 0)
+    return set_error(CMS_E_PARAM, "null argument");
+  if (order != CMS_NEIGHBOR_ORDER_ID && order != CMS_NEIGHBOR_ORDER_FASTIDSET)
+    return set_error(CMS_E_PARAM, "order must be CMS_NEIGHBOR_ORDER_ID or CMS_NEIGHBOR_ORDER_FASTIDSET");
+  if (threshold != threshold) return set_error(CMS_E_PARAM, "threshold must not be NaN");
+  Guard g(h);
+  int rc = require_finalized(h);
+  if (rc) return rc;
+  std::vector<int64_t> rows((size_t)nq);
+  for (int64_t i = 0; i < nq; ++i)
+    if ((rc = row_of(h, ids[i], &rows[(size_t)i]))) return rc;
+  offsets[0] = 0;
+  *total = 0;
+  if (nq == 0) return CMS_OK;
+  if (!out_ids) out_scores = nullptr;
+  if ((rc = threshold_rows(h, rows.data(), nq, threshold, offsets, out_ids, out_scores, capacity, total))) return rc;
+  if (!out_ids) return CMS_OK;  // counted only
+  if (*total > capacity)
+    return set_error(CMS_E_PARAM, "threshold neighbours: %lld entries, capacity %lld", (long long)*total,
+                     (long long)capacity);
+  if (order == CMS_NEIGHBOR_ORDER_FASTIDSET) {
+    std::vector<int64_t> li;
+    std::vector<double> ls;
+    for (int64_t q = 0; q < nq; ++q) {
+      const int64_t m = offsets[q + 1] - offsets[q];
+      int64_t* oi = out_ids + offsets[q];
+      li.assign(oi, oi + m);  // ascending IDs
+      if (fastidset_to_array(li.data(), m, oi) != m)
+        return set_error(CMS_E_PARAM, "an owner ID equal to a FastIDSet sentinel cannot be a neighbour");
+      if (!out_scores) continue;
+      double* os = out_scores + offsets[q];
+      ls.assign(os, os + m);
+      for (int64_t t = 0; t < m; ++t) os[t] = ls[(size_t)(std::lower_bound(li.begin(), li.end(), oi[t]) - li.begin())];
+    }
+  }
+  return CMS_OK;
+}
+
+int cms_fastidset_to_array(const int64_t* ids, int64_t n, int64_t* out, int64_t* count) {
+  if (n < 0 || !count || (n > 0 && (!ids || !out))) return set_error(CMS_E_PARAM, "null argument");
+  const int64_t c = fastidset_to_array(ids, n, out);
+  if (c < 0) return set_error(CMS_E_PARAM, "FastIDSet cannot hold its NULL / REMOVED sentinels (Long.MIN_VALUE, Long.MAX_VALUE)");
+  *count = c;
+  return CMS_OK;
 }
 
 // ---- anonymous profiles (cms_anonymous.hip) ----

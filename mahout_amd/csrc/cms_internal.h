@@ -228,6 +228,7 @@ struct Tunables {
   bool hot_routing = true; // CMS_NO_HOT_ROUTING=1: the partition sends every owner through both passes
   bool fp4 = true;         // CMS_NO_FP4=1: no e2m1 operand image (every single-limb pair on int8)
   bool mls = true;         // CMS_NO_MLS=1: multi-limb slabs on the 128-tile kernel instead of k_cosine_mls
+  int64_t threshold_slab_rows = 0;  // CMS_THRESHOLD_SLAB_ROWS: query rows per chunk of threshold_rows (0: slab_rows_for)
 };
 }  // namespace cms
 
@@ -686,6 +687,14 @@ struct TopQuery {
 int launch_top_k(cms_handle* h, const double* slab, const std::vector<TopQuery>& qs, int32_t k, const int64_t* d_perm,
                  int64_t* d_ids, double* d_scores, int32_t* d_counts);
 int64_t slab_rows_for(int64_t n);
+// ---- cms_threshold.hip: every owner at or above a similarity ----
+// ThresholdUserNeighborhood lists of the owner rows rows[0, nq) (any order,
+// repeats allowed) as a host CSR: offsets [nq + 1] and *total are always
+// complete; out_ids / out_scores (host, ascending owner row within a list;
+// out_scores may be null) are written while the running total fits capacity.
+// out_ids null: counts only.
+int threshold_rows(cms_handle* h, const int64_t* rows, int64_t nq, double threshold, int64_t* offsets, int64_t* out_ids,
+                   double* out_scores, int64_t capacity, int64_t* total);
 // slab rows of one multi-limb chunk of the all-pairs job (memory permitting, up to 4096 at 1M)
 int64_t multi_slab_rows(cms_handle* h, int64_t n);
 // ---- cms_anonymous.hip: profiles that are no row of the table ----
@@ -725,6 +734,9 @@ int java_double_to_string(double v, char* out, int cap);
 // candidates, TopItems.getTopItems) around the device estimates
 void recommend_candidates(const int64_t* nb_rows, int64_t m, int64_t user_row, const int64_t* pref_offsets,
                           const int64_t* pref_items, bool include_known, std::vector<int64_t>& out);
+// toArray() of a new FastIDSet() after add(ids[0..n)) in order into out
+// (room for n); returns the entry count, or -1 when an ID is a sentinel
+int64_t fastidset_to_array(const int64_t* ids, int64_t n, int64_t* out);
 int32_t recommend_top_items(int32_t how_many, const int64_t* items, const float* est, int64_t q, int64_t* out_items,
                             float* out_values);
 void parallel_users(int64_t n, int threads, const std::function<void(int64_t)>& fn);

@@ -223,6 +223,21 @@ void recommend_candidates(const int64_t* nb_rows, int64_t m, int64_t user_row, c
     if (k != kNull && k != kRemoved) out.push_back(k);
 }
 
+// new FastIDSet(), add(ids[i]) in order, toArray(): the iteration order
+// getUserNeighborhood hands to doEstimatePreference
+// (ThresholdUserNeighborhood.java:80-97, FastIDSet.java toArray)
+int64_t fastidset_to_array(const int64_t* ids, int64_t n, int64_t* out) {
+  FastIdSet s;
+  for (int64_t i = 0; i < n; ++i) {
+    if (ids[i] == kNull || ids[i] == kRemoved) return -1;  // checkArgument in FastIDSet.add
+    s.add(ids[i]);
+  }
+  int64_t c = 0;
+  for (int64_t k : s.keys)
+    if (k != kNull && k != kRemoved) out[c++] = k;
+  return c;
+}
+
 // TopItems.getTopItems with no rescorer; returns the list length (<= how_many)
 int32_t recommend_top_items(int32_t how_many, const int64_t* items, const float* est, int64_t q, int64_t* out_items,
                             float* out_values) {

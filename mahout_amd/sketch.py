@@ -308,6 +308,43 @@ class SketchTable:
                                        _ptr(cnt)))
         return ids, sc, cnt
 
+    _NEIGHBOR_ORDERS = {"id": _lib.CMS_NEIGHBOR_ORDER_ID, "fastidset": _lib.CMS_NEIGHBOR_ORDER_FASTIDSET}
+
+    def threshold_neighbors(self, owner_ids, threshold, order="id", scores=True, capacity=None):
+        """ThresholdUserNeighborhood lists of many owners (cms_threshold_neighbors):
+        every other owner whose similarity is not NaN and >= threshold.
+        order "id": ascending owner ID; "fastidset": FastIDSet.toArray() order,
+        what getUserNeighborhood returns.  Returns (offsets [nq + 1], ids,
+        scores or None): owner_ids[q]'s list is ids[offsets[q]:offsets[q + 1]].
+        One call with a guessed capacity (or `capacity` entries), and one
+        more with the exact total when that was short."""
+        q = np.ascontiguousarray(owner_ids, np.int64).reshape(-1)
+        nq, n = q.size, self.num_owners
+        off = np.zeros(nq + 1, np.int64)
+        total = ctypes.c_int64()
+        cap = min(nq * (n - 1), max(1 << 20, 64 * nq)) if capacity is None else max(0, int(capacity))
+        for attempt in range(2):
+            ids = np.zeros(max(cap, 1), np.int64)
+            sc = np.zeros(max(cap, 1), np.float64) if scores else None
+            rc = self._lib.cms_threshold_neighbors(self._h, _ptr(q), nq, float(threshold), self._NEIGHBOR_ORDERS[order],
+                                                   _ptr(off), _ptr(ids), _ptr(sc), cap, ctypes.byref(total))
+            if rc == _lib.CMS_E_PARAM and attempt == 0 and total.value > cap and off[-1] == total.value:
+                cap = total.value  # refused for room alone: the exact size is known now
+                continue
+            check(rc)
+            break
+        t = total.value
+        return off, ids[:t], (sc[:t] if scores else None)
+
+    def threshold_neighbor_counts(self, owner_ids, threshold):
+        """The list lengths threshold_neighbors would return (count-only call)."""
+        q = np.ascontiguousarray(owner_ids, np.int64).reshape(-1)
+        off = np.zeros(q.size + 1, np.int64)
+        total = ctypes.c_int64()
+        check(self._lib.cms_threshold_neighbors(self._h, _ptr(q), q.size, float(threshold), _lib.CMS_NEIGHBOR_ORDER_ID,
+                                                _ptr(off), None, None, 0, ctypes.byref(total)))
+        return np.diff(off)
+
     def estimate_preferences(self, user_id, neighbor_ids, item_keys, capper=None):
         """doEstimatePreference(user, neighbourhood, item) for every item key
         (CosineCM point-query path); capper = (min, max) or None."""
@@ -791,6 +828,16 @@ class SketchTable:
 
     def reset_timing(self):
         check(self._lib.cms_reset_timing(self._h))
+
+
+def fastidset_to_array(ids):
+    """toArray() of a new FastIDSet() after add(ids[i]) in order
+    (cms_fastidset_to_array: the library's own FastIDSet, host only)."""
+    ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+    out = np.zeros(max(ids.size, 1), np.int64)
+    cnt = ctypes.c_int64()
+    check(_lib.load().cms_fastidset_to_array(_ptr(ids), ids.size, _ptr(out), ctypes.byref(cnt)))
+    return out[:cnt.value]
 
 
 def shard_of_keys(keys, world):

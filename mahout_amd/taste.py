@@ -462,6 +462,57 @@ class NearestNUserNeighborhood:
         return off, np.ascontiguousarray(nb, np.int64)
 
 
+class ThresholdUserNeighborhood:
+    """ThresholdUserNeighborhood(threshold, similarity, model[, samplingRate]):
+    every other user whose similarity is not NaN and at least the threshold
+    (T/impl/neighborhood/ThresholdUserNeighborhood.java:77-97), in the order
+    the reference returns them: toArray() of the FastIDSet the users were added
+    to in getUserIDs() order.  One device selection per call
+    (SketchTable.threshold_neighbors) instead of a userSimilarity per pair."""
+
+    def __init__(self, threshold, userSimilarity, dataModel, samplingRate=1.0):
+        if userSimilarity is None or dataModel is None:
+            raise ValueError("userSimilarity or dataModel is null")
+        if np.isnan(threshold):
+            raise ValueError("threshold must not be NaN")
+        if not samplingRate == 1.0:
+            # the reference samples users with its own random generator
+            # (SamplingLongPrimitiveIterator); a rate below 1 has no defined
+            # answer to reproduce, and rates outside (0, 1] it refuses itself
+            raise ValueError("samplingRate must be 1.0: the reference's random user sampling is not reproduced")
+        self.threshold = float(threshold)
+        self._sim = userSimilarity
+        self._model = dataModel
+
+    def _lists(self, userIDs):
+        try:
+            off, ids, _ = self._sim.table.threshold_neighbors(userIDs, self.threshold, order="fastidset", scores=False)
+        except _lib.CmsError as e:
+            raise _map_error(e, "user")
+        return off, ids
+
+    def getUserNeighborhood(self, userID):
+        if userID == PlusAnonymousUserDataModel.TEMP_USER_ID and isinstance(self._model, PlusAnonymousUserDataModel):
+            # the temporary user is no row of the table: its similarities with
+            # every owner, then the reference's loop on the host
+            keys, vals = self._model.getPreferencesFromUser(userID)
+            owners = np.asarray(self._model.getDelegate().getUserIDs(), np.int64)
+            try:
+                sims = self._sim.table.anonymous_similarities(keys, vals, owners)
+            except _lib.CmsError as e:
+                raise _map_error(e, "user")
+            keep = FastIDSet()
+            for o in owners[~np.isnan(sims) & (sims >= self.threshold)].tolist():
+                keep.add(o)
+            return np.array(keep.toList(), np.int64)
+        return self._lists([userID])[1]
+
+    def getUserNeighborhoods(self, userIDs):
+        """getUserNeighborhood for many users: (offsets, neighbour IDs), each
+        list in FastIDSet order (one cms_threshold_neighbors call)."""
+        return self._lists(np.ascontiguousarray(userIDs, np.int64))
+
+
 class GenericUserBasedRecommender:
     """GenericUserBasedRecommender(model, neighborhood, CosineCM): the
     estimate path with the sketch point query
