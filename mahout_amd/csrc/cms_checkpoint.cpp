@@ -183,7 +183,9 @@ uint64_t merge_increment(const DirEntry& e) {
   switch (e.form) {
     case kRowList:
       if (e.len <= 2) return 0;  // (no entries)
-      cap = 255;                 // a list row's counters are below 2^8
+      // every key may share a bucket: the loader bounds a list's length, not a bucket's count (a list a build
+      // stored has counters below 2^8, and a cbound that says so)
+      cap = (uint64_t)kListMaxKeys;
       break;
     case kRowU1: cap = 1; break;
     case kRowU2: cap = 3; break;
@@ -218,8 +220,8 @@ int compact_form(uint32_t cmax, uint64_t mass, const uint64_t* row_sums, int dep
                                                : kRowU16;
     const uint64_t m = mass;
     const uint64_t limit = (uint64_t)(list_keys < kListMaxKeys ? list_keys : kListMaxKeys);
-    // (cmax <= 255: the writers re-count a list row's entries in u8 counters -- k_widen_rows, k_ckpt_add_lists -- as
-    // the builder's own lists allow them to; a row with a fuller bucket stays dense)
+    // (cmax <= 255: the in-place writers re-count a live list row's entries in u8 counters -- k_widen_rows -- as the
+    // builder's own lists allow them to; a row with a fuller bucket stays dense)
     bool list = frac_bits == 0 && narrow && 2 * dw <= 80 * 1024 && list_keys > 0 && row_sums != nullptr && cmax <= 255;
     for (int i = 0; list && i < depth; ++i) list = row_sums[i] == m;
     if (list && m >= 1 && m <= limit && (uint64_t)d * m <= (uint64_t)kListMaxEntries &&

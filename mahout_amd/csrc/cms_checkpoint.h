@@ -100,8 +100,9 @@ const char* check_merge_params(const Header& hd, const int64_t* live_a, const in
 // old + inc >= 2^32).  nullptr: every row fits (always for fp64 counters).
 const char* check_merge_masses(const Header& hd, const DirEntry* dir, const uint64_t* live_mass, int64_t n);
 // the most the image's row can add to one counter of the live row: min(cbound,
-// mass) for a form row (a list's counters are bounded the same way), the mass
-// for a hot or fp64 row, 0 for a row that stores nothing
+// mass) for a form row (a list's counters are bounded the same way, and by
+// kListMaxKeys: every key of a loaded list may share a bucket), the mass for a
+// hot or fp64 row, 0 for a row that stores nothing
 uint64_t merge_increment(const DirEntry& e);
 
 // ---- subtracting an image from a live table (cms_subtract_table) ----

@@ -24,22 +24,21 @@
 // cms_merge_table adds an image into a live table (a count-min sketch is
 // linear).  Every check precedes every write: k_ckpt_unpack<false> verifies
 // the whole resident image without a store, then the in-place writers'
-// promote / widen step prepares the live rows, then
-//
-//   k_ckpt_add        dense image rows of any form into dense live rows of
-//                     any form, on the unpack's source-driven tile mapping
-//   k_ckpt_add_lists  list image rows, one workgroup per row, counted in LDS
-//
+// promote / widen step prepares the live rows, then the image is applied.
 // cms_subtract_table is the other half: image B's stream being a sub-stream of
 // the live table's, table - B is the table of the remaining stream.  After the
 // same verify pass a second pass compares every image counter with its live
 // counter, in whatever form either row is in, and stores nothing; only then
-// are live list rows rewritten densely (widen_rows) and the image subtracted:
+// are live list rows rewritten densely (widen_rows) and the image subtracted.
+// Adding, comparing and subtracting are one statement, instantiated by
+// Apply::kAdd / kCheck / kSub:
 //
-//   k_ckpt_sub<false / true>       dense image rows against dense live rows,
-//                                  on k_ckpt_add's mapping: compare, or subtract
-//   k_ckpt_sub_rows<false / true>  rows where either side is a list, one
-//                                  workgroup per row, counted in LDS
+//   k_ckpt_apply<Op>        dense image rows of any form against dense live
+//                           rows of any form, on the unpack's source-driven
+//                           tile mapping
+//   k_ckpt_apply_lists<Op>  list image rows into dense live rows (kAdd, kSub),
+//                           one workgroup per row, counted in LDS
+//   k_ckpt_check_rows       the check of the rows where either side is a list
 //
 // The payload offsets are summed on the host from the directory's read-back
 // (64-bit: 16-byte units of a 79 GB arena pass 2^32); the same read-back
@@ -306,95 +305,160 @@ __global__ __launch_bounds__(256) void k_ckpt_expand(const int32_t* rows, const 
   }
 }
 
-// ---- merge: the image's rows added into the live rows (cms_merge_table) ----
+// ---- apply: a group of image counters meets a live row (cms_merge_table, cms_subtract_table) ----
 //
-// The source's form is independent of the destination's: promote_rows and
-// widen_rows ran first on the rows' bounds, so every live row that receives
-// anything is dense -- a 1-bit ... u16 row in a place that holds it, or a u32
-// hot slot -- and no field of it carries.  A group of N source counters
-// (N = 16, or 8 from a u16 chunk and from the list re-count) lands on N tb / 8
-// whole bytes of the destination, aligned to their own size, that no other
-// lane touches: a plain load, add, store.
+// The image row's form is independent of the live row's.  A group of N image
+// counters (N = 16; 8 from a u16 chunk, 4 from a u32 chunk) faces N tb / 8
+// whole bytes of the live row, aligned to their own size, that no other lane
+// touches, and is applied in one of three ways:
+//
+//   kAdd    promote_rows and widen_rows ran first on the rows' bounds, so
+//           every live row that receives anything is dense -- a 1-bit ... u16
+//           row in a place that holds it, or a u32 hot slot -- and no field of
+//           it carries: the N values packed into words, one integer add each
+//   kCheck  the group is loaded and compared field by field; true when any
+//           live field is below its image counter; nothing is stored
+//   kSub    follows a check that passed for the whole image: every decrement
+//           fits its field, so the packed words subtract with one integer
+//           subtract each and no borrow crosses a field
+//
+// A subtraction promotes nothing, so a u32 image row can face a narrow live
+// row.  That gives the one group below a byte -- four u32 image counters on a
+// 1-bit live row, half a byte that the next lane's chunk shares: kSub takes it
+// with an atomic on the aligned word.  An add never meets it (a u32 image row
+// forces a hot live row) and has no such store.
 
-struct AddDst {
+enum class Apply { kAdd, kCheck, kSub };
+
+struct ApplyDst {
   uint8_t* p;  // the live row's first byte
-  int tb;      // bits per counter: a narrow form's 1 .. 16, 32 for a hot slot; 0: the row takes no adds
+  int tb;      // bits per counter: a narrow form's 1 .. 16, 32 for a hot slot; 0: a list row, or the shared zero row
 };
-__device__ __forceinline__ AddDst add_dst(const TableView& tv, int64_t r) {
+__device__ __forceinline__ ApplyDst apply_dst(const TableView& tv, int64_t r) {
   const int32_t s = tv.hidx[r];
-  if (s >= 0) return AddDst{reinterpret_cast<uint8_t*>(tv.hot + (int64_t)s * tv.dw), 32};
+  if (s >= 0) return ApplyDst{reinterpret_cast<uint8_t*>(tv.hot + (int64_t)s * tv.dw), 32};
   const int64_t o = tv.off[r];
-  if (s == kFormList || o == 0) return AddDst{nullptr, 0};  // (widen_rows rewrote these: never the shared zero row)
-  return AddDst{reinterpret_cast<uint8_t*>(tv.t16 + (o & ~kCapMask)), form_bits(s)};
+  if (s == kFormList || o == 0) return ApplyDst{nullptr, 0};
+  return ApplyDst{reinterpret_cast<uint8_t*>(tv.t16 + (o & ~kCapMask)), form_bits(s)};
 }
 
-// counters [j, j + N) of the TB-bit row at p += v
-template <int TB, int N>
-__device__ __forceinline__ void add_fields(uint8_t* p, int64_t j, const uint32_t (&v)[N]) {
+// x (op)= y, word by word
+template <Apply Op>
+__device__ __forceinline__ void apply_word(uint32_t& x, uint32_t y) {
+  if constexpr (Op == Apply::kAdd) x += y; else x -= y;
+}
+
+// counters [j, j + N) of the TB-bit row at p against v; the load and store shapes follow from TB N alone
+template <int TB, int N, Apply Op>
+__device__ __forceinline__ bool apply_fields(uint8_t* p, int64_t j, const uint32_t (&v)[N]) {
   constexpr int kBits = TB * N;
+  constexpr uint32_t kMask = (1u << TB) - 1u;
+  static_assert(kBits >= 8 || Op != Apply::kAdd, "a plain add below a byte would race with the neighbouring lane");
   uint8_t* q = p + ((j * TB) >> 3);
+  bool under = false;
   if constexpr (kBits >= 32) {
     constexpr int kWords = kBits / 32, kPer = 32 / TB;
-    uint32_t inc[kWords];
-#pragma unroll
-    for (int k = 0; k < kWords; ++k) {
-      inc[k] = 0;
-#pragma unroll
-      for (int c = 0; c < kPer; ++c) inc[k] |= v[k * kPer + c] << (c * TB);
-    }
+    uint32_t x[kWords];
     if constexpr (kWords % 4 == 0) {
 #pragma unroll
       for (int k = 0; k < kWords; k += 4) {
-        uint4* d = reinterpret_cast<uint4*>(q) + k / 4;
-        uint4 x = *d;
-        x.x += inc[k], x.y += inc[k + 1], x.z += inc[k + 2], x.w += inc[k + 3];
-        *d = x;
+        const uint4 y = reinterpret_cast<const uint4*>(q)[k / 4];
+        x[k] = y.x, x[k + 1] = y.y, x[k + 2] = y.z, x[k + 3] = y.w;
       }
     } else if constexpr (kWords == 2) {
-      uint2* d = reinterpret_cast<uint2*>(q);
-      uint2 x = *d;
-      x.x += inc[0], x.y += inc[1];
-      *d = x;
+      const uint2 y = *reinterpret_cast<const uint2*>(q);
+      x[0] = y.x, x[1] = y.y;
     } else {
-      *reinterpret_cast<uint32_t*>(q) += inc[0];
+      x[0] = *reinterpret_cast<const uint32_t*>(q);
+    }
+    if constexpr (Op == Apply::kCheck) {
+#pragma unroll
+      for (int k = 0; k < kWords; ++k)
+#pragma unroll
+        for (int c = 0; c < kPer; ++c) under |= ((x[k] >> (c * TB)) & kMask) < v[k * kPer + c];
+    } else {
+#pragma unroll
+      for (int k = 0; k < kWords; ++k) {
+        uint32_t pk = 0;
+#pragma unroll
+        for (int c = 0; c < kPer; ++c) pk |= v[k * kPer + c] << (c * TB);
+        apply_word<Op>(x[k], pk);
+      }
+      if constexpr (kWords % 4 == 0) {
+#pragma unroll
+        for (int k = 0; k < kWords; k += 4) reinterpret_cast<uint4*>(q)[k / 4] = make_uint4(x[k], x[k + 1], x[k + 2], x[k + 3]);
+      } else if constexpr (kWords == 2) {
+        *reinterpret_cast<uint2*>(q) = make_uint2(x[0], x[1]);
+      } else {
+        *reinterpret_cast<uint32_t*>(q) = x[0];
+      }
     }
   } else {
-    uint32_t inc = 0;
+    const int sh = kBits < 8 ? (int)((j * TB) & 7) : 0;  // (4 bits: the low or the high half of the byte)
+    if constexpr (Op == Apply::kCheck) {
+      const uint32_t x = (kBits == 16 ? (uint32_t)*reinterpret_cast<const uint16_t*>(q) : (uint32_t)*q) >> sh;
 #pragma unroll
-    for (int c = 0; c < N; ++c) inc |= v[c] << (c * TB);
-    if constexpr (kBits == 16) *reinterpret_cast<uint16_t*>(q) += (uint16_t)inc;
-    else *q += (uint8_t)inc;
+      for (int c = 0; c < N; ++c) under |= ((x >> (c * TB)) & kMask) < v[c];
+    } else {
+      uint32_t pk = 0;
+#pragma unroll
+      for (int c = 0; c < N; ++c) pk |= v[c] << (c * TB);
+      if constexpr (kBits == 16) {
+        uint32_t x = *reinterpret_cast<const uint16_t*>(q);
+        apply_word<Op>(x, pk);
+        *reinterpret_cast<uint16_t*>(q) = (uint16_t)x;
+      } else if constexpr (kBits == 8) {
+        uint32_t x = *q;
+        apply_word<Op>(x, pk);
+        *q = (uint8_t)x;
+      } else if (pk) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(q);
+        atomicSub(reinterpret_cast<uint32_t*>(a & ~uintptr_t(3)), pk << (sh + 8 * (int)(a & 3)));
+      }
+    }
   }
+  return under;
 }
 
-// counters [j, j + cnt) of the live row += v[0 .. cnt) (j % N == 0; v past cnt
-// is zero: a narrow row's last partial group adds nothing to the slack of its
-// own slot, a hot row -- whose neighbour follows at once -- stops at cnt)
-template <int N>
-__device__ __forceinline__ void add_hot(uint32_t* d, const uint32_t (&v)[N], int cnt) {
+// counters [0, cnt) of the u32 row at d against v: a hot row's neighbour follows at once, so a partial group stops
+// at cnt, and only a whole aligned group goes as uint4
+template <int N, Apply Op>
+__device__ __forceinline__ bool apply_hot(uint32_t* d, const uint32_t (&v)[N], int cnt) {
+  bool under = false;
   if (cnt == N && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
 #pragma unroll
     for (int k = 0; k < N; k += 4) {
       uint4 x = reinterpret_cast<uint4*>(d)[k / 4];
-      x.x += v[k], x.y += v[k + 1], x.z += v[k + 2], x.w += v[k + 3];
-      reinterpret_cast<uint4*>(d)[k / 4] = x;
+      if constexpr (Op == Apply::kCheck) {
+        under |= x.x < v[k] || x.y < v[k + 1] || x.z < v[k + 2] || x.w < v[k + 3];
+      } else {
+        apply_word<Op>(x.x, v[k]), apply_word<Op>(x.y, v[k + 1]), apply_word<Op>(x.z, v[k + 2]), apply_word<Op>(x.w, v[k + 3]);
+        reinterpret_cast<uint4*>(d)[k / 4] = x;
+      }
     }
   } else {
 #pragma unroll
     for (int k = 0; k < N; ++k)
-      if (k < cnt) d[k] += v[k];
+      if (k < cnt) {
+        if constexpr (Op == Apply::kCheck) under |= d[k] < v[k];
+        else apply_word<Op>(d[k], v[k]);
+      }
   }
+  return under;
 }
-template <int N>
-__device__ __forceinline__ void add_counters(const AddDst& dst, int64_t j, const uint32_t (&v)[N], int cnt) {
+
+// counters [j, j + cnt) of the live row against v[0 .. cnt) (j % N == 0; v past cnt is zero: a narrow row's last
+// partial group leaves the slack of its own slot as it is).  True: kCheck found a live field below its image counter.
+template <int N, Apply Op>
+__device__ __forceinline__ bool apply_counters(const ApplyDst& dst, int64_t j, const uint32_t (&v)[N], int cnt) {
   switch (dst.tb) {
-    case 32: add_hot<N>(reinterpret_cast<uint32_t*>(dst.p) + j, v, cnt); break;
-    case 16: add_fields<16, N>(dst.p, j, v); break;
-    case 8: add_fields<8, N>(dst.p, j, v); break;
-    case 4: add_fields<4, N>(dst.p, j, v); break;
-    case 2: add_fields<2, N>(dst.p, j, v); break;
-    case 1: add_fields<1, N>(dst.p, j, v); break;
-    default: break;
+    case 32: return apply_hot<N, Op>(reinterpret_cast<uint32_t*>(dst.p) + j, v, cnt);
+    case 16: return apply_fields<16, N, Op>(dst.p, j, v);
+    case 8: return apply_fields<8, N, Op>(dst.p, j, v);
+    case 4: return apply_fields<4, N, Op>(dst.p, j, v);
+    case 2: return apply_fields<2, N, Op>(dst.p, j, v);
+    case 1: return apply_fields<1, N, Op>(dst.p, j, v);
+    default: return false;
   }
 }
 
@@ -423,14 +487,19 @@ __device__ __forceinline__ bool chunk_counters(const uint32_t (&w)[4], int g, ui
 }
 
 // Dense image rows (1-bit ... u16, u32 hot, fp64) of the resident payload src
-// added into the live table: k_ckpt_unpack's source-driven mapping, where
-// sv.addr[s] is the segment's owner row and a list segment is left to
-// k_ckpt_add_lists.  A lane takes one 16-byte chunk: 128 / sb counters of one
-// row.  t64: the fp64 table (then every segment is an fp64 row).  out[1] |=
-// kBadDest when a live row is in no state to take adds (the driver's
-// promote / widen step makes that impossible).
-__global__ __launch_bounds__(256) void k_ckpt_add(SegView sv, uint64_t c1, const uint8_t* src, TableView tv, double* t64,
-                                                  unsigned long long* out) {
+// against dense live rows, any of the six widths on either side:
+// k_ckpt_unpack's source-driven mapping, where sv.addr[s] is the segment's
+// owner row and a segment flagged kListBit is another kernel's, or applies
+// nothing.  A lane takes one 16-byte chunk: 128 / sb counters of one row.
+//   kAdd    t64: the fp64 table (then every segment is an fp64 row)
+//   kCheck  out[1] |= kBadUnder and out[2] = min(out[2], owner row) where a
+//           live counter is below the image's; no store to the table
+// out[1] |= kBadDest when a live row is in no state for the operation: a list
+// or the zero row (the driver's promote / widen step, or its row routing,
+// makes that impossible), or for an add a narrow row under u32 counters.
+template <Apply Op>
+__global__ __launch_bounds__(256) void k_ckpt_apply(SegView sv, uint64_t c1, const uint8_t* src, TableView tv, double* t64,
+                                                    unsigned long long* out) {
   __shared__ uint64_t s_off[kTileChunks + 1];
   unsigned long long bad = 0;
   const int64_t dw = tv.dw;
@@ -451,255 +520,18 @@ __global__ __launch_bounds__(256) void k_ckpt_add(SegView sv, uint64_t c1, const
       const int rem = (int)min<uint64_t>(len - rel, 16);
       const uint4 x = *reinterpret_cast<const uint4*>(src + pos);
       const uint32_t w[4] = {x.x, x.y, x.z, x.w};
-      if (t64) {  // one correctly rounded add per counter (always done: x + 0.0 is not x for every x)
-        double* d = t64 + r * dw + (int64_t)(rel >> 3);
-        d[0] += __longlong_as_double((long long)((uint64_t)w[0] | ((uint64_t)w[1] << 32)));
-        if (rem == 16) d[1] += __longlong_as_double((long long)((uint64_t)w[2] | ((uint64_t)w[3] << 32)));
-        continue;
+      if constexpr (Op == Apply::kAdd) {
+        if (t64) {  // one correctly rounded add per counter (always done: x + 0.0 is not x for every x)
+          double* d = t64 + r * dw + (int64_t)(rel >> 3);
+          d[0] += __longlong_as_double((long long)((uint64_t)w[0] | ((uint64_t)w[1] << 32)));
+          if (rem == 16) d[1] += __longlong_as_double((long long)((uint64_t)w[2] | ((uint64_t)w[3] << 32)));
+          continue;
+        }
       }
       if ((w[0] | w[1] | w[2] | w[3]) == 0) continue;  // (most chunks of a sparse 1- or 2-bit row)
-      const AddDst dst = add_dst(tv, r);
+      const ApplyDst dst = apply_dst(tv, r);
       const int sb = (int)((len * 8) / (uint64_t)dw);
-      if (dst.tb == 0 || (sb == 32 && dst.tb != 32)) {
-        bad |= kBadDest;
-        continue;
-      }
-      uint32_t v[16];
-      switch (sb) {
-        case 32: {  // u32 -> u32
-          const uint32_t v4[4] = {w[0], w[1], w[2], w[3]};
-          add_hot<4>(reinterpret_cast<uint32_t*>(dst.p) + (int64_t)(rel >> 2), v4, rem >> 2);
-          break;
-        }
-        case 16: {
-          uint32_t v8[8];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) v8[q] = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
-          add_counters<8>(dst, (int64_t)(rel >> 1), v8, rem >> 1);
-          break;
-        }
-        case 8:
-          chunk_counters<8>(w, 0, v);
-          add_counters<16>(dst, (int64_t)rel, v, 16);
-          break;
-        case 4:
-#pragma unroll 1
-          for (int g = 0; g < 2; ++g)
-            if (chunk_counters<4>(w, g, v)) add_counters<16>(dst, (int64_t)rel * 2 + 16 * g, v, 16);
-          break;
-        case 2:
-#pragma unroll 1
-          for (int g = 0; g < 4; ++g)
-            if (chunk_counters<2>(w, g, v)) add_counters<16>(dst, (int64_t)rel * 4 + 16 * g, v, 16);
-          break;
-        case 1:
-#pragma unroll 1
-          for (int g = 0; g < 8; ++g)
-            if (chunk_counters<1>(w, g, v)) add_counters<16>(dst, (int64_t)rel * 8 + 16 * g, v, 16);
-          break;
-        default: bad |= kBadDest; break;
-      }
-    }
-    __syncthreads();
-  }
-  if (bad) atomicOr(out + 1, bad);
-}
-
-// List image rows: one workgroup per listed row (rows[i], its payload offset
-// off[i] and key count m[i] from the validated directory).  A list's entries
-// scatter, so each sketch row is counted in LDS first (u8 counters, four per
-// word, as k_widen_rows' re-count: a list row's counters are below 2^8), then
-// every lane adds groups of 8 counters -- at least one whole byte of the
-// narrowest form -- skipping the groups that counted nothing.  The workgroup
-// owns the live row: no global atomics.  The verify pass checked every entry;
-// the bound test below only keeps LDS safe should the caller's device image
-// change under the call.
-__global__ __launch_bounds__(256) void k_ckpt_add_lists(const int32_t* rows, const uint64_t* off, const uint32_t* lm,
-                                                        int64_t count, const uint8_t* src, TableView tv, int depth,
-                                                        unsigned long long* out) {
-  extern __shared__ uint32_t lc[];  // [w / 4]
-  const int w = tv.w;
-  for (int64_t i = blockIdx.x; i < count; i += gridDim.x) {
-    const int64_t r = rows[i];
-    const uint16_t* e = reinterpret_cast<const uint16_t*>(src + off[i]) + 1;
-    const uint32_t m = lm[i];
-    const AddDst dst = add_dst(tv, r);
-    if (dst.tb == 0) {  // (uniform over the workgroup)
-      if (threadIdx.x == 0) atomicOr(out + 1, (unsigned long long)kBadDest);
-      continue;
-    }
-    for (int rr = 0; rr < depth; ++rr) {
-      for (int j = threadIdx.x; j < (w >> 2); j += 256) lc[j] = 0u;
-      __syncthreads();
-      for (uint32_t t = threadIdx.x; t < m; t += 256) {
-        const uint32_t b = e[(uint32_t)rr * m + t];
-        if (b < (uint32_t)w) atomicAdd(&lc[b >> 2], 1u << ((b & 3u) * 8u));
-      }
-      __syncthreads();
-      for (int q = threadIdx.x; q < (w >> 3); q += 256) {
-        const uint32_t lo = lc[2 * q], hi = lc[2 * q + 1];
-        if ((lo | hi) == 0) continue;
-        const uint32_t v[8] = {lo & 255u, (lo >> 8) & 255u, (lo >> 16) & 255u, lo >> 24,
-                               hi & 255u, (hi >> 8) & 255u, (hi >> 16) & 255u, hi >> 24};
-        add_counters<8>(dst, (int64_t)rr * w + 8 * q, v, 8);
-      }
-      __syncthreads();  // the counts are added before the next sketch row zeroes them
-    }
-  }
-}
-
-// ---- subtract: the image's rows compared with, then taken out of, the live rows (cms_subtract_table) ----
-//
-// The addressing is the add's: a group of N source counters faces N tb / 8
-// whole bytes of the live row that no other lane touches.  kWrite = false is
-// the check -- the group is loaded and compared field by field, true when any
-// live field is below its image counter, and nothing is stored.  kWrite =
-// true follows a check that passed for the whole image: every decrement fits
-// its field, so the packed word of decrements subtracts with one integer
-// subtract and no borrow crosses a field.  The one group below a byte -- four
-// u32 image counters on a 1-bit live row, half a byte that the next lane's
-// chunk shares -- subtracts with an atomic on the aligned word.
-
-template <int TB, int N, bool kWrite>
-__device__ __forceinline__ bool sub_fields(uint8_t* p, int64_t j, const uint32_t (&v)[N]) {
-  constexpr int kBits = TB * N;
-  constexpr uint32_t kMask = (1u << TB) - 1u;
-  uint8_t* q = p + ((j * TB) >> 3);
-  bool under = false;
-  if constexpr (kBits >= 32) {
-    constexpr int kWords = kBits / 32, kPer = 32 / TB;
-    uint32_t x[kWords];
-    if constexpr (kWords % 4 == 0) {
-#pragma unroll
-      for (int k = 0; k < kWords; k += 4) {
-        const uint4 y = reinterpret_cast<const uint4*>(q)[k / 4];
-        x[k] = y.x, x[k + 1] = y.y, x[k + 2] = y.z, x[k + 3] = y.w;
-      }
-    } else if constexpr (kWords == 2) {
-      const uint2 y = *reinterpret_cast<const uint2*>(q);
-      x[0] = y.x, x[1] = y.y;
-    } else {
-      x[0] = *reinterpret_cast<const uint32_t*>(q);
-    }
-    if constexpr (kWrite) {
-#pragma unroll
-      for (int k = 0; k < kWords; ++k) {
-        uint32_t dec = 0;
-#pragma unroll
-        for (int c = 0; c < kPer; ++c) dec |= v[k * kPer + c] << (c * TB);
-        x[k] -= dec;
-      }
-      if constexpr (kWords % 4 == 0) {
-#pragma unroll
-        for (int k = 0; k < kWords; k += 4) reinterpret_cast<uint4*>(q)[k / 4] = make_uint4(x[k], x[k + 1], x[k + 2], x[k + 3]);
-      } else if constexpr (kWords == 2) {
-        *reinterpret_cast<uint2*>(q) = make_uint2(x[0], x[1]);
-      } else {
-        *reinterpret_cast<uint32_t*>(q) = x[0];
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < kWords; ++k)
-#pragma unroll
-        for (int c = 0; c < kPer; ++c) under |= ((x[k] >> (c * TB)) & kMask) < v[k * kPer + c];
-    }
-  } else {
-    const int sh = kBits < 8 ? (int)((j * TB) & 7) : 0;  // (4 bits: the low or the high half of the byte)
-    if constexpr (kWrite) {
-      uint32_t dec = 0;
-#pragma unroll
-      for (int c = 0; c < N; ++c) dec |= v[c] << (c * TB);
-      if constexpr (kBits == 16) {
-        *reinterpret_cast<uint16_t*>(q) -= (uint16_t)dec;
-      } else if constexpr (kBits == 8) {
-        *q -= (uint8_t)dec;
-      } else if (dec) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(q);
-        atomicSub(reinterpret_cast<uint32_t*>(a & ~uintptr_t(3)), dec << (sh + 8 * (int)(a & 3)));
-      }
-    } else {
-      const uint32_t x = (kBits == 16 ? (uint32_t)*reinterpret_cast<const uint16_t*>(q) : (uint32_t)*q) >> sh;
-#pragma unroll
-      for (int c = 0; c < N; ++c) under |= ((x >> (c * TB)) & kMask) < v[c];
-    }
-  }
-  return under;
-}
-
-// counters [0, cnt) of the u32 row at d (add_hot's care at a hot row's end: the next hot row is never touched)
-template <int N, bool kWrite>
-__device__ __forceinline__ bool sub_hot(uint32_t* d, const uint32_t (&v)[N], int cnt) {
-  bool under = false;
-  if (cnt == N && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
-#pragma unroll
-    for (int k = 0; k < N; k += 4) {
-      uint4 x = reinterpret_cast<uint4*>(d)[k / 4];
-      if constexpr (kWrite) {
-        x.x -= v[k], x.y -= v[k + 1], x.z -= v[k + 2], x.w -= v[k + 3];
-        reinterpret_cast<uint4*>(d)[k / 4] = x;
-      } else {
-        under |= x.x < v[k] || x.y < v[k + 1] || x.z < v[k + 2] || x.w < v[k + 3];
-      }
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-      if (k < cnt) {
-        if constexpr (kWrite) d[k] -= v[k];
-        else under |= d[k] < v[k];
-      }
-  }
-  return under;
-}
-// (v past cnt is zero, as for add_counters)
-template <int N, bool kWrite>
-__device__ __forceinline__ bool sub_counters(const AddDst& dst, int64_t j, const uint32_t (&v)[N], int cnt) {
-  switch (dst.tb) {
-    case 32: return sub_hot<N, kWrite>(reinterpret_cast<uint32_t*>(dst.p) + j, v, cnt);
-    case 16: return sub_fields<16, N, kWrite>(dst.p, j, v);
-    case 8: return sub_fields<8, N, kWrite>(dst.p, j, v);
-    case 4: return sub_fields<4, N, kWrite>(dst.p, j, v);
-    case 2: return sub_fields<2, N, kWrite>(dst.p, j, v);
-    case 1: return sub_fields<1, N, kWrite>(dst.p, j, v);
-    default: return false;
-  }
-}
-
-// Dense image rows against dense live rows, any of the six widths on either
-// side: k_ckpt_add's mapping (a segment flagged kListBit is another kernel's,
-// or subtracts nothing).  A u32 image row faces a narrow live row here -- a
-// subtraction promotes nothing, and after the check every value fits the live
-// field.  kWrite = false: out[1] |= kBadUnder and out[2] = min(out[2], owner
-// row) where a live counter is below the image's; no store to the table.
-// out[1] |= kBadDest when a live row is a list or on the zero row (the driver
-// routes those to k_ckpt_sub_rows).
-template <bool kWrite>
-__global__ __launch_bounds__(256) void k_ckpt_sub(SegView sv, uint64_t c1, const uint8_t* src, TableView tv,
-                                                  unsigned long long* out) {
-  __shared__ uint64_t s_off[kTileChunks + 1];
-  unsigned long long bad = 0;
-  const int64_t dw = tv.dw;
-  const uint64_t tiles = (c1 + kTileChunks - 1) / kTileChunks;
-  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
-    const uint64_t t0 = t * kTileChunks, t1 = min<uint64_t>(t0 + (uint64_t)kTileChunks, c1);
-    int64_t first;
-    int cnt;
-    tile_setup(sv, t0, s_off, first, cnt);
-    for (uint64_t c = t0 + threadIdx.x; c < t1; c += 256) {
-      const uint64_t pos = c * 16;
-      const int i = tile_find(s_off, cnt, pos);
-      const int64_t s = first + i;
-      const uint64_t rel = pos - s_off[i];
-      const uint64_t len = sv.len[s];
-      if ((len & kListBit) || rel >= len) continue;
-      const int64_t r = (int64_t)sv.addr[s];
-      const int rem = (int)min<uint64_t>(len - rel, 16);
-      const uint4 x = *reinterpret_cast<const uint4*>(src + pos);
-      const uint32_t w[4] = {x.x, x.y, x.z, x.w};
-      if ((w[0] | w[1] | w[2] | w[3]) == 0) continue;
-      const AddDst dst = add_dst(tv, r);
-      const int sb = (int)((len * 8) / (uint64_t)dw);
-      if (dst.tb == 0) {
+      if (dst.tb == 0 || (Op == Apply::kAdd && sb == 32 && dst.tb != 32)) {
         bad |= kBadDest;
         continue;
       }
@@ -708,45 +540,104 @@ __global__ __launch_bounds__(256) void k_ckpt_sub(SegView sv, uint64_t c1, const
       switch (sb) {
         case 32: {
           const uint32_t v4[4] = {w[0], w[1], w[2], w[3]};
-          under = sub_counters<4, kWrite>(dst, (int64_t)(rel >> 2), v4, rem >> 2);
+          if constexpr (Op == Apply::kAdd)  // u32 -> u32 only
+            apply_hot<4, Op>(reinterpret_cast<uint32_t*>(dst.p) + (int64_t)(rel >> 2), v4, rem >> 2);
+          else
+            under = apply_counters<4, Op>(dst, (int64_t)(rel >> 2), v4, rem >> 2);
           break;
         }
         case 16: {
           uint32_t v8[8];
 #pragma unroll
           for (int q = 0; q < 8; ++q) v8[q] = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
-          under = sub_counters<8, kWrite>(dst, (int64_t)(rel >> 1), v8, rem >> 1);
+          under = apply_counters<8, Op>(dst, (int64_t)(rel >> 1), v8, rem >> 1);
           break;
         }
         case 8:
           chunk_counters<8>(w, 0, v);
-          under = sub_counters<16, kWrite>(dst, (int64_t)rel, v, 16);
+          under = apply_counters<16, Op>(dst, (int64_t)rel, v, 16);
           break;
         case 4:
 #pragma unroll 1
           for (int g = 0; g < 2; ++g)
-            if (chunk_counters<4>(w, g, v)) under |= sub_counters<16, kWrite>(dst, (int64_t)rel * 2 + 16 * g, v, 16);
+            if (chunk_counters<4>(w, g, v)) under |= apply_counters<16, Op>(dst, (int64_t)rel * 2 + 16 * g, v, 16);
           break;
         case 2:
 #pragma unroll 1
           for (int g = 0; g < 4; ++g)
-            if (chunk_counters<2>(w, g, v)) under |= sub_counters<16, kWrite>(dst, (int64_t)rel * 4 + 16 * g, v, 16);
+            if (chunk_counters<2>(w, g, v)) under |= apply_counters<16, Op>(dst, (int64_t)rel * 4 + 16 * g, v, 16);
           break;
         case 1:
 #pragma unroll 1
           for (int g = 0; g < 8; ++g)
-            if (chunk_counters<1>(w, g, v)) under |= sub_counters<16, kWrite>(dst, (int64_t)rel * 8 + 16 * g, v, 16);
+            if (chunk_counters<1>(w, g, v)) under |= apply_counters<16, Op>(dst, (int64_t)rel * 8 + 16 * g, v, 16);
           break;
         default: bad |= kBadDest; break;
       }
-      if (under) {
-        bad |= kBadUnder;
-        atomicMin(out + 2, (unsigned long long)r);
+      if constexpr (Op == Apply::kCheck) {
+        if (under) {
+          bad |= kBadUnder;
+          atomicMin(out + 2, (unsigned long long)r);
+        }
       }
     }
     __syncthreads();
   }
   if (bad) atomicOr(out + 1, bad);
+}
+
+// List image rows into dense live rows (kAdd, kSub): one workgroup per listed
+// row (rows[i], its payload offset off[i] and key count lm[i] from the
+// validated directory).  Shapes with lists have w % 32 == 0.  A list's entries
+// scatter, so each sketch row is counted in LDS first, upward from zero in u16
+// cells, two per word: a list holds at most kListMaxKeys = 1024 keys and the
+// loader accepts any such list -- all of them may share a bucket -- so a count
+// can pass 2^8 and stays below 2^16.  Then every lane takes groups of 16 cells,
+// skipping the groups that counted nothing.  The workgroup owns the live row:
+// no global atomics.  out[1] |= kBadDest for a live row that is a list or on
+// the zero row (widen_rows rewrote those).  The verify pass checked every
+// entry; the b < w test only keeps LDS safe should the caller's device image
+// change under the call.
+template <Apply Op>
+__global__ __launch_bounds__(256) void k_ckpt_apply_lists(const int32_t* rows, const uint64_t* off, const uint32_t* lm,
+                                                          int64_t count, const uint8_t* src, TableView tv, int depth,
+                                                          unsigned long long* out) {
+  static_assert(Op != Apply::kCheck, "the check of a list row is k_ckpt_check_rows'");
+  extern __shared__ __align__(16) uint32_t lc[];  // [w / 2]
+  const int w = tv.w;
+  // The cells are zeroed once: the lane that finds counts in a group puts zeros back, so every sketch row of every
+  // listed row starts from zero cells without another pass over all of them.
+  for (int j = threadIdx.x; j < (w >> 1); j += 256) lc[j] = 0u;
+  __syncthreads();
+  for (int64_t i = blockIdx.x; i < count; i += gridDim.x) {
+    const int64_t r = rows[i];
+    const uint16_t* e = reinterpret_cast<const uint16_t*>(src + off[i]) + 1;
+    const uint32_t m = lm[i];
+    const ApplyDst dst = apply_dst(tv, r);
+    if (dst.tb == 0) {  // (uniform over the workgroup)
+      if (threadIdx.x == 0) atomicOr(out + 1, (unsigned long long)kBadDest);
+      continue;
+    }
+    for (int rr = 0; rr < depth; ++rr) {
+      for (uint32_t t = threadIdx.x; t < m; t += 256) {
+        const uint32_t b = e[(uint32_t)rr * m + t];
+        if (b < (uint32_t)w) atomicAdd(&lc[b >> 1], 1u << ((b & 1u) * 16u));
+      }
+      __syncthreads();
+      for (int g = threadIdx.x; g < (w >> 4); g += 256) {
+        uint4* cells = reinterpret_cast<uint4*>(lc) + 2 * g;  // the group's 16 cells
+        const uint4 lo = cells[0], hi = cells[1];
+        if ((lo.x | lo.y | lo.z | lo.w | hi.x | hi.y | hi.z | hi.w) == 0) continue;
+        cells[0] = cells[1] = make_uint4(0u, 0u, 0u, 0u);
+        const uint32_t x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        uint32_t v[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) v[q] = (q & 1) ? x[q >> 1] >> 16 : x[q >> 1] & 0xFFFFu;
+        apply_counters<16, Op>(dst, (int64_t)rr * w + 16 * g, v, 16);
+      }
+      __syncthreads();  // the groups are read and zeroed before the next sketch row counts into them
+    }
+  }
 }
 
 // The live list rows about to be rewritten (bound[r] != 0: the row's own
@@ -771,28 +662,24 @@ __device__ __forceinline__ void row_counters16(int32_t f, const uint8_t* p8, int
   }
 }
 
-// Rows where either side is a list: one workgroup per listed row (rows[i], the
-// image row's payload offset off[i], its form sform[i] -- kFormList, a narrow
-// form, or 0 for u32 counters -- and a list's key count lm[i], all from the
-// validated directory).  Shapes with lists have w % 32 == 0.  Per sketch row
-// an LDS image of w u16 halves starts at the bias 2^14; every entry of a live
-// list adds one to its bucket's half, every entry of an image list takes one
-// off.  An image list holds at most kListMaxKeys = 1024 keys and the loader
-// accepts any such list -- all of them may share a bucket -- so a count can
-// pass the 2^8 that the add's u8 image relies on for built rows; u16 halves
-// around the bias hold +-1024 and no carry or borrow leaves a half.  Then each
-// lane takes groups of 16 counters: live = dense live counter (0 for a list)
-// + half - bias, image = dense image counter (0 for a list).
-//   kWrite = false  live < image anywhere: out[1] |= kBadUnder, out[2] = min(out[2], row); no store
-//   kWrite = true   image list rows only, the live row dense (widen_rows rewrote the live lists): the counts leave
-//                   through sub_counters; the workgroup owns the live row
-// The verify pass checked every image entry and the build or the loader every
-// live one; the e < w tests only keep LDS safe.
-template <bool kWrite>
-__global__ __launch_bounds__(256) void k_ckpt_sub_rows(const int32_t* rows, const uint64_t* off, const int32_t* sform,
-                                                       const uint32_t* lm, int64_t count, const uint8_t* src, TableView tv,
-                                                       int depth, unsigned long long* out) {
-  extern __shared__ uint32_t lc[];  // [w / 2]
+// The subtraction's check of the rows where either side is a list: one
+// workgroup per listed row (rows[i], the image row's payload offset off[i],
+// its form sform[i] -- kFormList, a narrow form, or 0 for u32 counters -- and
+// a list's key count lm[i], all from the validated directory); no store to
+// the table.  Per sketch row an LDS image of w u16 halves starts at the bias
+// 2^14; every entry of a live list adds one to its bucket's half, every entry
+// of an image list takes one off (a live list adds and an image list takes,
+// hence the bias; either holds at most 1024 keys, so no carry or borrow leaves
+// a half).  Then each lane takes groups of 16 counters: live = dense live
+// counter (0 for a list) + half - bias, image = dense image counter (0 for a
+// list); live < image anywhere: out[1] |= kBadUnder, out[2] = min(out[2],
+// row).  out[1] |= kBadDest for a live row on the zero row.  The verify pass
+// checked every image entry and the build or the loader every live one; the
+// b < w tests only keep LDS safe.
+__global__ __launch_bounds__(256) void k_ckpt_check_rows(const int32_t* rows, const uint64_t* off, const int32_t* sform,
+                                                         const uint32_t* lm, int64_t count, const uint8_t* src, TableView tv,
+                                                         int depth, unsigned long long* out) {
+  extern __shared__ __align__(16) uint32_t lc[];  // [w / 2]
   constexpr uint32_t kBias = 0x4000u;
   const int w = tv.w;
   for (int64_t i = blockIdx.x; i < count; i += gridDim.x) {
@@ -803,9 +690,8 @@ __global__ __launch_bounds__(256) void k_ckpt_sub_rows(const int32_t* rows, cons
     const uint32_t sm = sf == kFormList ? lm[i] : 0u;
     const int32_t lf = tv.hidx[r];
     const bool live_list = lf == kFormList;
-    const AddDst dst = add_dst(tv, r);  // (tb == 0: a list, or the zero row)
-    const bool live_zero = dst.tb == 0 && !live_list;
-    if (live_zero || (kWrite && (live_list || sf != kFormList))) {  // (uniform over the workgroup; the driver sends no such row)
+    const ApplyDst dst = apply_dst(tv, r);  // (tb == 0: a list, or the zero row)
+    if (dst.tb == 0 && !live_list) {  // (uniform over the workgroup; the driver sends no such row)
       if (threadIdx.x == 0) atomicOr(out + 1, (unsigned long long)kBadDest);
       continue;
     }
@@ -834,36 +720,28 @@ __global__ __launch_bounds__(256) void k_ckpt_sub_rows(const int32_t* rows, cons
           differs |= x[k] ^ (kBias | (kBias << 16));
         }
         auto half = [&](int q) { return (q & 1) ? x[q >> 1] >> 16 : x[q >> 1] & 0xFFFFu; };
-        if constexpr (kWrite) {
-          if (!differs) continue;  // the image's list has no entry in this group
-          uint32_t dec[16];
+        // One side at least is a list, so at most one dense group is loaded.  An image list only takes from
+        // the bias and a live list only adds to it, so each comparison stays in 32 bits.
+        uint32_t v[16];
+        if (sf == kFormList) {
+          if (!differs) continue;  // no net entry in this group: nothing is taken from it, the live group is not read
+          if (live_list) {
 #pragma unroll
-          for (int q = 0; q < 16; ++q) dec[q] = kBias - half(q);
-          sub_counters<16, true>(dst, j, dec, 16);
-        } else {
-          // One side at least is a list, so at most one dense group is loaded.  An image list only takes from
-          // the bias and a live list only adds to it, so each comparison stays in 32 bits.
-          uint32_t v[16];
-          if (sf == kFormList) {
-            if (!differs) continue;  // no net entry in this group: nothing is taken from it, the live group is not read
-            if (live_list) {
+            for (int q = 0; q < 16; ++q) under |= half(q) < kBias;
+          } else {
+            row_counters16(dst.tb == 32 ? 0 : lf, dst.p, j, v);
 #pragma unroll
-              for (int q = 0; q < 16; ++q) under |= half(q) < kBias;
-            } else {
-              row_counters16(dst.tb == 32 ? 0 : lf, dst.p, j, v);
-#pragma unroll
-              for (int q = 0; q < 16; ++q) under |= v[q] < kBias - half(q);
-            }
-          } else {  // a dense image row against a live list: read whole, zero wherever the list has no entry
-            row_counters16(sf, sp, j, v);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) under |= v[q] > half(q) - kBias;
+            for (int q = 0; q < 16; ++q) under |= v[q] < kBias - half(q);
           }
+        } else {  // a dense image row against a live list: read whole, zero wherever the list has no entry
+          row_counters16(sf, sp, j, v);
+#pragma unroll
+          for (int q = 0; q < 16; ++q) under |= v[q] > half(q) - kBias;
         }
       }
       __syncthreads();  // the halves are read before the next sketch row resets them
     }
-    if (!kWrite && under) {
+    if (under) {
       atomicOr(out + 1, (unsigned long long)kBadUnder);
       atomicMin(out + 2, (unsigned long long)r);
     }
@@ -1050,6 +928,37 @@ struct TmpRemover {
   ~TmpRemover() { std::remove(path.c_str()); }
 };
 
+// body(f, ok) writes an image to path + ".tmp" (ok = false: a short write; its
+// own status for any other failure); the file is closed and renamed to path
+// only when all of it was written.  The time from open to close is "ckpt_io".
+template <class Body>
+int write_atomically(cms_handle* h, const char* path, Body&& body) {
+  const std::string tmp = std::string(path) + ".tmp";
+  TmpRemover cleanup{tmp};  // (declared before the file: it is closed first)
+  File out;
+  out.f = std::fopen(tmp.c_str(), "wb");
+  if (!out.f) return set_error(CMS_E_PARAM, "cannot open %s for writing", tmp.c_str());
+  const auto t_io = std::chrono::steady_clock::now();
+  bool ok = true;
+  if (int rc = body(out.f, ok)) return rc;
+  const bool closed = std::fclose(out.f) == 0;
+  out.f = nullptr;
+  add_host_time(h, "ckpt_io", t_io);
+  if (!ok || !closed) return set_error(CMS_E_PARAM, "short write to %s", tmp.c_str());
+  if (std::rename(tmp.c_str(), path) != 0) return set_error(CMS_E_PARAM, "cannot rename %s to %s", tmp.c_str(), path);
+  return CMS_OK;
+}
+
+// header, IDs (and the gap before the directory), directory: the image's first payload_off bytes
+std::vector<uint8_t> image_head(const Image& im) {
+  const Header& hd = im.hd;
+  std::vector<uint8_t> head((size_t)hd.payload_off, 0);
+  std::memcpy(head.data(), &hd, sizeof(hd));
+  if (!im.ids.empty()) std::memcpy(head.data() + hd.ids_off, im.ids.data(), (size_t)hd.ids_bytes);
+  std::memcpy(head.data() + hd.dir_off, im.dir.data(), (size_t)hd.dir_bytes);
+  return head;
+}
+
 int save_file(cms_handle* h, const char* path) {
   Image im;
   int rc = plan_save(h, im);
@@ -1060,59 +969,44 @@ int save_file(cms_handle* h, const char* path) {
   DevBuf d_out;
   CMS_HIP(d_out.ensure(2 * sizeof(unsigned long long)));
   CMS_HIP(hipMemsetAsync(d_out.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
-  const std::string tmp = std::string(path) + ".tmp";
-  TmpRemover cleanup{tmp};  // (declared before the file: it is closed first)
-  File out;
-  out.f = std::fopen(tmp.c_str(), "wb");
-  if (!out.f) return set_error(CMS_E_PARAM, "cannot open %s for writing", tmp.c_str());
   const Header& hd = im.hd;
-  bool ok = true;
-  const auto t_io = std::chrono::steady_clock::now();
-  {  // header (its checksum follows the payload), IDs, directory
-    static const char zeros[16] = {};
-    ok = ok && std::fwrite(&hd, sizeof(hd), 1, out.f) == 1;
-    if (!im.ids.empty()) ok = ok && std::fwrite(im.ids.data(), 8, im.ids.size(), out.f) == im.ids.size();
-    const uint64_t gap = hd.dir_off - (hd.ids_off + hd.ids_bytes);
-    if (gap) ok = ok && std::fwrite(zeros, 1, (size_t)gap, out.f) == gap;
-    ok = ok && std::fwrite(im.dir.data(), sizeof(DirEntry), im.dir.size(), out.f) == im.dir.size();
-  }
-  // the payload through two pinned buffers: pack of chunk i + 1 (the handle's
-  // stream) and D2H of chunk i (the side stream) run while the host writes
-  // chunk i - 1
-  const uint64_t total = hd.payload_bytes / 16, per = kIoChunk / 16;
-  const uint64_t nchunks = (total + per - 1) / per;
-  if (ok && nchunks > 0) {
-    Staging st;
-    if ((rc = st.init(std::min(kIoChunk, hd.payload_bytes)))) return rc;
-    for (uint64_t i = 0; i <= nchunks && ok; ++i) {
-      if (i < nchunks) {
-        const int b = (int)(i & 1);
-        const uint64_t c0 = i * per, c1 = std::min(total, c0 + per);
-        if (i >= 2) CMS_HIP(hipStreamWaitEvent(h->stream, st.ev_b[b], 0));  // the copy out of dev[b] is done
-        if ((rc = pack_range(h, sg, c0, c1, st.dev[b].as<uint8_t>(), d_out.as<unsigned long long>()))) return rc;
-        CMS_HIP(hipEventRecord(st.ev_a[b], h->stream));
-        CMS_HIP(hipStreamWaitEvent(h->side_stream, st.ev_a[b], 0));
-        CMS_HIP(hipMemcpyAsync(st.pin[b], st.dev[b].ptr, (size_t)((c1 - c0) * 16), hipMemcpyDeviceToHost, h->side_stream));
-        CMS_HIP(hipEventRecord(st.ev_b[b], h->side_stream));
-      }
-      if (i >= 1) {
-        const uint64_t j = i - 1, c0 = j * per, c1 = std::min(total, c0 + per);
-        CMS_HIP(hipEventSynchronize(st.ev_b[j & 1]));
-        ok = std::fwrite(st.pin[j & 1], 16, (size_t)(c1 - c0), out.f) == c1 - c0;
+  return write_atomically(h, path, [&](FILE* f, bool& ok) -> int {
+    // header (its checksum follows the payload), IDs, directory
+    const std::vector<uint8_t> head = image_head(im);
+    ok = std::fwrite(head.data(), 1, head.size(), f) == head.size();
+    // the payload through two pinned buffers: pack of chunk i + 1 (the handle's
+    // stream) and D2H of chunk i (the side stream) run while the host writes
+    // chunk i - 1
+    const uint64_t total = hd.payload_bytes / 16, per = kIoChunk / 16;
+    const uint64_t nchunks = (total + per - 1) / per;
+    if (ok && nchunks > 0) {
+      Staging st;
+      if (int r = st.init(std::min(kIoChunk, hd.payload_bytes))) return r;
+      for (uint64_t i = 0; i <= nchunks && ok; ++i) {
+        if (i < nchunks) {
+          const int b = (int)(i & 1);
+          const uint64_t c0 = i * per, c1 = std::min(total, c0 + per);
+          if (i >= 2) CMS_HIP(hipStreamWaitEvent(h->stream, st.ev_b[b], 0));  // the copy out of dev[b] is done
+          if (int r = pack_range(h, sg, c0, c1, st.dev[b].as<uint8_t>(), d_out.as<unsigned long long>())) return r;
+          CMS_HIP(hipEventRecord(st.ev_a[b], h->stream));
+          CMS_HIP(hipStreamWaitEvent(h->side_stream, st.ev_a[b], 0));
+          CMS_HIP(hipMemcpyAsync(st.pin[b], st.dev[b].ptr, (size_t)((c1 - c0) * 16), hipMemcpyDeviceToHost, h->side_stream));
+          CMS_HIP(hipEventRecord(st.ev_b[b], h->side_stream));
+        }
+        if (i >= 1) {
+          const uint64_t j = i - 1, c0 = j * per, c1 = std::min(total, c0 + per);
+          CMS_HIP(hipEventSynchronize(st.ev_b[j & 1]));
+          ok = std::fwrite(st.pin[j & 1], 16, (size_t)(c1 - c0), f) == c1 - c0;
+        }
       }
     }
-  }
-  unsigned long long res[2] = {0, 0};
-  CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
-  CMS_HIP(hipStreamSynchronize(h->stream));
-  im.hd.checksum = res[0];
-  ok = ok && std::fseek(out.f, 0, SEEK_SET) == 0 && std::fwrite(&im.hd, sizeof(im.hd), 1, out.f) == 1;
-  const bool closed = std::fclose(out.f) == 0;
-  out.f = nullptr;
-  add_host_time(h, "ckpt_io", t_io);
-  if (!ok || !closed) return set_error(CMS_E_PARAM, "short write to %s", tmp.c_str());
-  if (std::rename(tmp.c_str(), path) != 0) return set_error(CMS_E_PARAM, "cannot rename %s to %s", tmp.c_str(), path);
-  return CMS_OK;
+    unsigned long long res[2] = {0, 0};
+    CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+    CMS_HIP(hipStreamSynchronize(h->stream));
+    im.hd.checksum = res[0];
+    ok = ok && std::fseek(f, 0, SEEK_SET) == 0 && std::fwrite(&im.hd, sizeof(im.hd), 1, f) == 1;
+    return CMS_OK;
+  });
 }
 
 int save_device(cms_handle* h, void* d_buf, int64_t capacity, int64_t* bytes) {
@@ -1138,11 +1032,7 @@ int save_device(cms_handle* h, void* d_buf, int64_t capacity, int64_t* bytes) {
   CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
   CMS_HIP(hipStreamSynchronize(h->stream));
   im.hd.checksum = res[0];
-  // header, IDs (and the gap before the directory), directory
-  std::vector<uint8_t> head((size_t)hd.payload_off, 0);
-  std::memcpy(head.data(), &im.hd, sizeof(im.hd));
-  if (!im.ids.empty()) std::memcpy(head.data() + hd.ids_off, im.ids.data(), (size_t)hd.ids_bytes);
-  std::memcpy(head.data() + hd.dir_off, im.dir.data(), (size_t)hd.dir_bytes);
+  const std::vector<uint8_t> head = image_head(im);
   CMS_HIP(hipMemcpyAsync(base, head.data(), head.size(), hipMemcpyHostToDevice, h->stream));
   CMS_HIP(hipStreamSynchronize(h->stream));
   return CMS_OK;
@@ -1389,28 +1279,54 @@ int commit_load(cms_handle* h, const Image& im, Expand& ex, const unsigned long 
   return CMS_OK;
 }
 
+// the file at path opened and its header read and validated (the file is left just past the header)
+int read_header_file(File& in, const char* path, Header& hd) {
+  in.f = std::fopen(path, "rb");
+  if (!in.f) return set_error(CMS_E_PARAM, "cannot open %s", path);
+  if (std::fseek(in.f, 0, SEEK_END) != 0) return set_error(CMS_E_PARAM, "cannot seek in %s", path);
+  const long long size = (long long)std::ftell(in.f);
+  std::rewind(in.f);
+  if (size < (long long)sizeof(Header) || std::fread(&hd, sizeof(Header), 1, in.f) != 1)
+    return set_error(CMS_E_PARAM, "checkpoint %s: shorter than a checkpoint header", path);
+  if (const char* why = check_header(hd, (uint64_t)size)) return set_error(CMS_E_PARAM, "checkpoint %s: %s", path, why);
+  return CMS_OK;
+}
+
+// An image's head -- header, IDs, directory -- read from the file at path,
+// validated and matched against the handle; the file is left at the payload.
+int read_head_file(File& in, const char* path, cms_handle* h, Image& im) {
+  int rc = read_header_file(in, path, im.hd);
+  if (rc) return rc;
+  if ((rc = check_matches(h, im.hd))) return rc;
+  std::vector<uint8_t> head((size_t)im.hd.payload_off);
+  std::rewind(in.f);
+  if (std::fread(head.data(), 1, head.size(), in.f) != head.size())
+    return set_error(CMS_E_PARAM, "checkpoint %s: short read", path);
+  return parse_head(head.data(), im);
+}
+
+// The same of a device image of `bytes` bytes at d_buf (synchronises the handle's stream).
+int read_head_device(const void* d_buf, int64_t bytes, cms_handle* h, Image& im) {
+  if (bytes < (int64_t)sizeof(Header)) return set_error(CMS_E_PARAM, "checkpoint image: shorter than a checkpoint header");
+  if (reinterpret_cast<uintptr_t>(d_buf) & 15) return set_error(CMS_E_PARAM, "device image must be 16-byte aligned");
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  CMS_HIP(hipMemcpy(&im.hd, d_buf, sizeof(Header), hipMemcpyDeviceToHost));
+  if (const char* why = check_header(im.hd, (uint64_t)bytes)) return set_error(CMS_E_PARAM, "checkpoint image: %s", why);
+  if (int rc = check_matches(h, im.hd)) return rc;
+  std::vector<uint8_t> head((size_t)im.hd.payload_off);
+  CMS_HIP(hipMemcpy(head.data(), d_buf, head.size(), hipMemcpyDeviceToHost));
+  if (std::memcmp(head.data(), &im.hd, sizeof(Header)) != 0)
+    return set_error(CMS_E_PARAM, "checkpoint image changed while it was read");
+  return parse_head(head.data(), im);
+}
+
 int load_file(cms_handle* h, const char* path) {
   int rc = check_loadable(h, "cms_load_table");
   if (rc) return rc;
   File in;
-  in.f = std::fopen(path, "rb");
-  if (!in.f) return set_error(CMS_E_PARAM, "cannot open %s", path);
   Image im;
-  if (std::fseek(in.f, 0, SEEK_END) != 0) return set_error(CMS_E_PARAM, "cannot seek in %s", path);
-  const long long size = (long long)std::ftell(in.f);
-  std::rewind(in.f);
-  if (size < (long long)sizeof(Header) || std::fread(&im.hd, sizeof(Header), 1, in.f) != 1)
-    return set_error(CMS_E_PARAM, "checkpoint %s: shorter than a checkpoint header", path);
-  if (const char* why = check_header(im.hd, (uint64_t)size)) return set_error(CMS_E_PARAM, "checkpoint %s: %s", path, why);
-  if ((rc = check_matches(h, im.hd))) return rc;
+  if ((rc = read_head_file(in, path, h, im))) return rc;
   const Header& hd = im.hd;
-  {
-    std::vector<uint8_t> head((size_t)hd.payload_off);
-    std::rewind(in.f);
-    if (std::fread(head.data(), 1, head.size(), in.f) != head.size())
-      return set_error(CMS_E_PARAM, "checkpoint %s: short read", path);
-    if ((rc = parse_head(head.data(), im))) return rc;
-  }
   // ---- every host check has passed: the device part ----
   CMS_HIP(hipStreamSynchronize(h->stream));
   Expand ex;
@@ -1462,21 +1378,9 @@ int load_file(cms_handle* h, const char* path) {
 int load_device(cms_handle* h, const void* d_buf, int64_t bytes) {
   int rc = check_loadable(h, "cms_load_table_device");
   if (rc) return rc;
-  if (bytes < (int64_t)sizeof(Header)) return set_error(CMS_E_PARAM, "checkpoint image: shorter than a checkpoint header");
-  if (reinterpret_cast<uintptr_t>(d_buf) & 15) return set_error(CMS_E_PARAM, "device image must be 16-byte aligned");
-  CMS_HIP(hipStreamSynchronize(h->stream));
   Image im;
-  CMS_HIP(hipMemcpy(&im.hd, d_buf, sizeof(Header), hipMemcpyDeviceToHost));
-  if (const char* why = check_header(im.hd, (uint64_t)bytes)) return set_error(CMS_E_PARAM, "checkpoint image: %s", why);
-  if ((rc = check_matches(h, im.hd))) return rc;
+  if ((rc = read_head_device(d_buf, bytes, h, im))) return rc;
   const Header& hd = im.hd;
-  {
-    std::vector<uint8_t> head((size_t)hd.payload_off);
-    CMS_HIP(hipMemcpy(head.data(), d_buf, head.size(), hipMemcpyDeviceToHost));
-    if (std::memcmp(head.data(), &im.hd, sizeof(Header)) != 0)
-      return set_error(CMS_E_PARAM, "checkpoint image changed while it was read");
-    if ((rc = parse_head(head.data(), im))) return rc;
-  }
   Expand ex;
   Segs sg;
   DevBuf d_out;
@@ -1506,7 +1410,7 @@ int load_device(cms_handle* h, const void* d_buf, int64_t bytes) {
 
 // The verify pass of a merge and of a subtraction: checksum, pad bytes and
 // every list row over the resident payload, no store.  Leaves the image's
-// segments in sg (a segment's address: its owner row, as k_ckpt_add reads it)
+// segments in sg (a segment's address: its owner row, as k_ckpt_apply reads it)
 // and d_out ([0] checksum, [1] kBad* flags, [2] an owner row) zeroed but [2],
 // which is all ones.
 int verify_resident(cms_handle* h, Image& im, const uint8_t* d_payload, Segs& sg, DevBuf& d_out) {
@@ -1536,178 +1440,185 @@ int verify_resident(cms_handle* h, Image& im, const uint8_t* d_payload, Segs& sg
   return CMS_OK;
 }
 
-// The image (head parsed and validated into im, payload resident at d_payload,
-// 16-byte aligned) added into the live table.  Every check -- the header-level
-// compatibility, the overflow rule, then the verify pass over the whole
-// payload -- precedes the first write: a refusal leaves the table as it was.
-int merge_resident(cms_handle* h, Image& im, const uint8_t* d_payload) {
+// the rows a one-workgroup-per-row kernel takes: owner row, the image row's form (kFormList, a narrow form, 0 for
+// u32 counters), its payload offset and a list's key count
+struct RowList {
+  std::vector<int32_t> row, form;
+  std::vector<uint64_t> off;
+  std::vector<uint32_t> m;
+  DevBuf d_row, d_form, d_off, d_m;
+  void push(int64_t r, const DirEntry& e, int depth) {
+    row.push_back((int32_t)r);
+    form.push_back(e.form == kRowHot ? 0 : table_form(e.form));
+    off.push_back(e.off);
+    m.push_back(e.form == kRowList ? (uint32_t)((e.len - 2) / (2 * (uint64_t)depth)) : 0u);
+  }
+  int upload(cms_handle* h) {
+    const size_t k = row.size();
+    if (k == 0) return CMS_OK;
+    CMS_HIP(d_row.ensure(sizeof(int32_t) * k));
+    CMS_HIP(d_form.ensure(sizeof(int32_t) * k));
+    CMS_HIP(d_off.ensure(sizeof(uint64_t) * k));
+    CMS_HIP(d_m.ensure(sizeof(uint32_t) * k));
+    CMS_HIP(hipMemcpyAsync(d_row.ptr, row.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, h->stream));
+    CMS_HIP(hipMemcpyAsync(d_form.ptr, form.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, h->stream));
+    CMS_HIP(hipMemcpyAsync(d_off.ptr, off.data(), sizeof(uint64_t) * k, hipMemcpyHostToDevice, h->stream));
+    CMS_HIP(hipMemcpyAsync(d_m.ptr, m.data(), sizeof(uint32_t) * k, hipMemcpyHostToDevice, h->stream));
+    return CMS_OK;
+  }
+};
+
+// One merge or subtraction in flight: what the shared opening leaves, what
+// the operation's own middle adds for the shared closing.  (The host arrays
+// of the uploads live here until the last synchronisation.)
+struct ApplyJob {
+  std::vector<uint64_t> mass;  // the live masses, then the new ones
+  Segs sg;                     // the image's segments (a segment's address: its owner row)
+  DevBuf d_out;                // [0] checksum, [1] kBad* flags, [2] an owner row
+  uint64_t chunks = 0;         // 16-byte chunks of the payload
+  RowList lists;               // the image's list rows that the write pass applies
+  std::vector<int64_t> touched;  // rows the image changes (the refresh marks them)
+  DevBuf d_touched;
+  std::vector<uint64_t> bound;  // the widen step's per-row bounds
+  std::vector<uint8_t> force;   // the promote step's rows that must hold u32 counters
+};
+
+// The checks a merge and a subtraction share, in this order: the header-level
+// compatibility, the mass rule of the operation, then the verify pass over
+// the whole payload.  No write.
+int apply_open(cms_handle* h, Apply op, Image& im, const uint8_t* d_payload, ApplyJob& job) {
   const Header& hd = im.hd;
   const int64_t n = h->n;
   if (const char* why = check_merge_params(hd, h->a, h->b, h->h_owner_ids.empty() ? nullptr : h->h_owner_ids.data(),
                                            im.ids.empty() ? nullptr : im.ids.data()))
     return set_error(CMS_E_PARAM, "checkpoint: %s", why);
   CMS_HIP(hipStreamSynchronize(h->stream));
-  std::vector<uint64_t> mass((size_t)n, 0);  // the live masses, then the merged ones
-  if (!h->empty) CMS_HIP(hipMemcpy(mass.data(), h->d_row_mass, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost));
-  if (const char* why = check_merge_masses(hd, im.dir.data(), mass.data(), n)) return set_error(CMS_E_OVERFLOW, "%s", why);
+  job.mass.assign((size_t)n, 0);
+  if (!h->empty) CMS_HIP(hipMemcpy(job.mass.data(), h->d_row_mass, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost));
+  if (const char* why = op == Apply::kAdd ? check_merge_masses(hd, im.dir.data(), job.mass.data(), n)
+                                          : check_subtract_masses(hd, im.dir.data(), job.mass.data(), n))
+    return set_error(CMS_E_OVERFLOW, "%s", why);
+  job.chunks = hd.payload_bytes / 16;
+  return verify_resident(h, im, d_payload, job.sg, job.d_out);
+}
 
-  Segs sg;
-  DevBuf d_out;
-  unsigned long long res[2] = {0, 0};
-  const uint64_t chunks = hd.payload_bytes / 16;
-  int rc = verify_resident(h, im, d_payload, sg, d_out);
-  if (rc) return rc;
+// cms_top_k_refresh stays incremental after a delta merge or subtraction
+int mark_touched(cms_handle* h, ApplyJob& job) {
+  if (!h->rf_valid || job.touched.empty()) return CMS_OK;
+  const size_t bytes = sizeof(int64_t) * job.touched.size();
+  CMS_HIP(job.d_touched.ensure(bytes));
+  CMS_HIP(hipMemcpyAsync(job.d_touched.ptr, job.touched.data(), bytes, hipMemcpyHostToDevice, h->stream));
+  return refresh_mark(h, job.d_touched.as<int64_t>(), (int64_t)job.touched.size());
+}
 
-  // ---- every check has passed: the first write follows ----
-  std::vector<int32_t> lrow;  // the image's list rows that hold entries
-  std::vector<uint64_t> loff;
-  std::vector<uint32_t> lm;
-  std::vector<int64_t> touched;  // rows the image adds to (the refresh marks them)
-  std::vector<uint64_t> bound;   // (host arrays of the uploads below live until the last synchronisation)
-  std::vector<uint8_t> force;
-  DevBuf d_lrow, d_loff, d_lm, d_touched;
+// One pass of the image over the live table: the dense rows' kernel over the
+// segments as job.sg was last uploaded, then the listed rows' kernel over rl.
+int launch_apply(cms_handle* h, Apply op, ApplyJob& job, RowList& rl, const uint8_t* d_payload) {
+  if (int rc = rl.upload(h)) return rc;
+  TimedScope ts(h, op == Apply::kAdd ? "ckpt_add" : op == Apply::kCheck ? "ckpt_subcheck" : "ckpt_sub");
+  unsigned long long* d_out = job.d_out.as<unsigned long long>();
+  if (job.chunks > 0) {
+    const auto dense = op == Apply::kAdd     ? k_ckpt_apply<Apply::kAdd>
+                       : op == Apply::kCheck ? k_ckpt_apply<Apply::kCheck>
+                                             : k_ckpt_apply<Apply::kSub>;
+    hipLaunchKernelGGL(dense, dim3(grid_for(h, job.chunks)), dim3(256), 0, h->stream, job.sg.view(), job.chunks, d_payload,
+                       h->tview(), h->f64 ? h->d_t64 : (double*)nullptr, d_out);
+  }
+  if (!rl.row.empty()) {
+    const dim3 g((unsigned)std::min<size_t>(rl.row.size(), 65536));
+    const size_t lds = 2 * (size_t)h->p.width;  // u16 cells
+    if (op == Apply::kCheck) {
+      hipLaunchKernelGGL(k_ckpt_check_rows, g, dim3(256), lds, h->stream, rl.d_row.as<int32_t>(), rl.d_off.as<uint64_t>(),
+                         rl.d_form.as<int32_t>(), rl.d_m.as<uint32_t>(), (int64_t)rl.row.size(), d_payload, h->tview(),
+                         (int)h->p.depth, d_out);
+    } else {
+      const auto lists = op == Apply::kAdd ? k_ckpt_apply_lists<Apply::kAdd> : k_ckpt_apply_lists<Apply::kSub>;
+      hipLaunchKernelGGL(lists, g, dim3(256), lds, h->stream, rl.d_row.as<int32_t>(), rl.d_off.as<uint64_t>(),
+                         rl.d_m.as<uint32_t>(), (int64_t)rl.row.size(), d_payload, h->tview(), (int)h->p.depth, d_out);
+    }
+  }
+  CMS_HIP(hipGetLastError());
+  return CMS_OK;
+}
+
+// d_out read back ([1]: the kBad* flags, [2]: an owner row), after everything queued so far
+int read_out(cms_handle* h, ApplyJob& job, unsigned long long (&res)[3]) {
+  CMS_HIP(hipMemcpyAsync(res, job.d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  return CMS_OK;
+}
+
+// The merge's own middle, the first write: the in-place writers' sequence
+// (ingest_coo_device) -- per-row bounds, promote, widen -- so that every live
+// row that receives anything is dense and no field of it carries.
+int merge_prepare(cms_handle* h, const Image& im, ApplyJob& job) {
+  const int64_t n = h->n;
+  int rc;
   if (h->f64) {
     if (h->empty) {
       CMS_HIP(hipMemsetAsync(h->d_t64, 0, sizeof(double) * (size_t)n * (size_t)h->dw, h->stream));
       CMS_HIP(hipMemsetAsync(h->d_row_mass, 0, sizeof(uint64_t) * (size_t)n, h->stream));
     }
     for (int64_t r = 0; r < n; ++r)
-      if (im.dir[r].len) touched.push_back(r);
-  } else {
-    // the in-place writers' sequence (ingest_coo_device): per-row bounds, promote, widen
-    bound.assign((size_t)n, 0);
-    force.assign((size_t)n, 0);
-    for (int64_t r = 0; r < n; ++r) {
-      const DirEntry& e = im.dir[r];
-      const uint64_t inc = merge_increment(e);
-      if (inc == 0) continue;  // (nothing stored, or every stored counter is zero: mass 0)
-      bound[r] = mass[r] + inc;
-      force[r] = e.form == kRowHot;  // a live row that receives u32 counters holds u32 counters
-      touched.push_back(r);
-      if (e.form == kRowList) {
-        lrow.push_back((int32_t)r);
-        loff.push_back(e.off);
-        lm.push_back((uint32_t)((e.len - 2) / (2 * (uint64_t)hd.depth)));
-      }
-    }
-    // rows that add nothing leave the segments: their live rows were not prepared for an add
-    for (size_t s = 0, r = 0; s < sg.len.size(); ++s) {
-      while (im.dir[r].len == 0) ++r;
-      if (bound[r] == 0) sg.len[s] |= kListBit;  // (k_ckpt_add skips list segments)
-      ++r;
-    }
-    if ((rc = sg.upload(h))) return rc;
-    if (h->empty) {  // as a COO batch into an empty table
-      if ((rc = reset_rows_zero(h))) return rc;
-      CMS_HIP(hipMemsetAsync(h->d_row_mass, 0, sizeof(uint64_t) * (size_t)n, h->stream));
-      h->norms_valid = false;
-    }
-    CMS_HIP(h->ws_bound.ensure(sizeof(uint64_t) * (size_t)n));
-    CMS_HIP(h->ws_force.ensure((size_t)n));
-    CMS_HIP(hipMemcpyAsync(h->ws_bound.ptr, bound.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    CMS_HIP(hipMemcpyAsync(h->ws_force.ptr, force.data(), (size_t)n, hipMemcpyHostToDevice, h->stream));
-    if ((rc = promote_rows(h, h->ws_bound.as<uint64_t>(), h->ws_force.as<uint8_t>(), true))) return rc;
-    if ((rc = widen_rows(h, h->ws_bound.as<uint64_t>(), h->d_row_mass, false))) return rc;
+      if (im.dir[r].len) job.touched.push_back(r);
+    return CMS_OK;
   }
-  if (h->rf_valid && !touched.empty()) {  // cms_top_k_refresh stays incremental after a delta merge
-    CMS_HIP(d_touched.ensure(sizeof(int64_t) * touched.size()));
-    CMS_HIP(hipMemcpyAsync(d_touched.ptr, touched.data(), sizeof(int64_t) * touched.size(), hipMemcpyHostToDevice, h->stream));
-    if ((rc = refresh_mark(h, d_touched.as<int64_t>(), (int64_t)touched.size()))) return rc;
+  Segs& sg = job.sg;
+  std::vector<uint64_t>& bound = job.bound;
+  bound.assign((size_t)n, 0);
+  job.force.assign((size_t)n, 0);
+  for (int64_t r = 0; r < n; ++r) {
+    const DirEntry& e = im.dir[r];
+    const uint64_t inc = merge_increment(e);
+    if (inc == 0) continue;  // (nothing stored, or every stored counter is zero: mass 0)
+    bound[r] = job.mass[r] + inc;
+    job.force[r] = e.form == kRowHot;  // a live row that receives u32 counters holds u32 counters
+    job.touched.push_back(r);
+    if (e.form == kRowList) job.lists.push(r, e, im.hd.depth);
   }
-  if (!lrow.empty()) {
-    const size_t k = lrow.size();
-    CMS_HIP(d_lrow.ensure(sizeof(int32_t) * k));
-    CMS_HIP(d_loff.ensure(sizeof(uint64_t) * k));
-    CMS_HIP(d_lm.ensure(sizeof(uint32_t) * k));
-    CMS_HIP(hipMemcpyAsync(d_lrow.ptr, lrow.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, h->stream));
-    CMS_HIP(hipMemcpyAsync(d_loff.ptr, loff.data(), sizeof(uint64_t) * k, hipMemcpyHostToDevice, h->stream));
-    CMS_HIP(hipMemcpyAsync(d_lm.ptr, lm.data(), sizeof(uint32_t) * k, hipMemcpyHostToDevice, h->stream));
+  // rows that add nothing leave the segments: their live rows were not prepared for an add
+  for (size_t s = 0, r = 0; s < sg.len.size(); ++s) {
+    while (im.dir[r].len == 0) ++r;
+    if (bound[r] == 0) sg.len[s] |= kListBit;  // (k_ckpt_apply skips list segments)
+    ++r;
   }
-  {
-    TimedScope ts(h, "ckpt_add");
-    if (chunks > 0)
-      hipLaunchKernelGGL(k_ckpt_add, dim3(grid_for(h, chunks)), dim3(256), 0, h->stream, sg.view(), chunks, d_payload,
-                         h->tview(), h->f64 ? h->d_t64 : (double*)nullptr, d_out.as<unsigned long long>());
-    if (!lrow.empty())
-      hipLaunchKernelGGL(k_ckpt_add_lists, dim3((unsigned)std::min<size_t>(lrow.size(), 65536)), dim3(256),
-                         (size_t)h->p.width, h->stream, d_lrow.as<int32_t>(), d_loff.as<uint64_t>(), d_lm.as<uint32_t>(),
-                         (int64_t)lrow.size(), d_payload, h->tview(), (int)h->p.depth, d_out.as<unsigned long long>());
-    CMS_HIP(hipGetLastError());
+  if ((rc = sg.upload(h))) return rc;
+  if (h->empty) {  // as a COO batch into an empty table
+    if ((rc = reset_rows_zero(h))) return rc;
+    CMS_HIP(hipMemsetAsync(h->d_row_mass, 0, sizeof(uint64_t) * (size_t)n, h->stream));
+    // (a handle that never built a row has never written its bounds: the widen step adds to them)
+    CMS_HIP(hipMemsetAsync(h->d_cbound, 0, sizeof(uint32_t) * (size_t)n, h->stream));
+    h->norms_valid = false;
   }
-  for (int64_t r = 0; r < n; ++r) mass[r] += im.dir[r].mass;  // the true masses, not the bounds
-  CMS_HIP(hipMemcpyAsync(h->d_row_mass, mass.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
-  CMS_HIP(hipStreamSynchronize(h->stream));
-  // "ingested, not finalized", as after a COO batch; cms_finalize re-derives norms and row maxima
-  h->pairs_ingested += hd.pairs_ingested;
-  h->empty = false;
-  h->norms_valid = false;
-  h->finalized = false;
-  h->stale_possible = true;
-  if (res[1] & kBadDest) return set_error(CMS_E_STATE, "cms_merge_table: a live row was in no form to take its adds");
-  return CMS_OK;
+  CMS_HIP(h->ws_bound.ensure(sizeof(uint64_t) * (size_t)n));
+  CMS_HIP(h->ws_force.ensure((size_t)n));
+  CMS_HIP(hipMemcpyAsync(h->ws_bound.ptr, bound.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  CMS_HIP(hipMemcpyAsync(h->ws_force.ptr, job.force.data(), (size_t)n, hipMemcpyHostToDevice, h->stream));
+  if ((rc = promote_rows(h, h->ws_bound.as<uint64_t>(), h->ws_force.as<uint8_t>(), true))) return rc;
+  return widen_rows(h, h->ws_bound.as<uint64_t>(), h->d_row_mass, false);
 }
 
-// The image subtracted from the live table (u32 counters).  The merge's
-// checks in the merge's order, with the mass rule turned round; then the
-// counter check over the whole image against the live rows as they are now --
-// list rows and all -- and only then the dense rewrite of the live list rows
-// that lose entries and the subtraction itself.
-int subtract_resident(cms_handle* h, Image& im, const uint8_t* d_payload) {
+// The subtraction's own middle: the counter check over the whole image
+// against the live rows as they are now -- list rows and all, no store -- and
+// only then the first write, the dense rewrite of the live list rows that
+// lose entries.  Leaves the segments routed for the write pass.
+int subtract_prepare(cms_handle* h, const Image& im, const uint8_t* d_payload, ApplyJob& job) {
   const Header& hd = im.hd;
   const int64_t n = h->n;
-  if (const char* why = check_merge_params(hd, h->a, h->b, h->h_owner_ids.empty() ? nullptr : h->h_owner_ids.data(),
-                                           im.ids.empty() ? nullptr : im.ids.data()))
-    return set_error(CMS_E_PARAM, "checkpoint: %s", why);
-  CMS_HIP(hipStreamSynchronize(h->stream));
-  std::vector<uint64_t> mass((size_t)n, 0);  // the live masses, then the remaining ones
-  if (!h->empty) CMS_HIP(hipMemcpy(mass.data(), h->d_row_mass, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost));
-  if (const char* why = check_subtract_masses(hd, im.dir.data(), mass.data(), n)) return set_error(CMS_E_OVERFLOW, "%s", why);
-  Segs sg;
-  DevBuf d_out;
-  const uint64_t chunks = hd.payload_bytes / 16;
-  int rc = verify_resident(h, im, d_payload, sg, d_out);
-  if (rc) return rc;
-  if (h->empty) return CMS_OK;  // every mass of the image is zero: nothing to take out of no counters
-
+  Segs& sg = job.sg;
+  int rc;
   // the live rows' states (12 bytes per owner, read back once beside the masses)
   std::vector<int32_t> hidx((size_t)n);
   std::vector<int64_t> off((size_t)n);
   CMS_HIP(hipMemcpy(hidx.data(), h->d_hidx, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
   CMS_HIP(hipMemcpy(off.data(), h->d_off, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost));
-  // The rows the image subtracts from, and which kernel takes each: a row
-  // whose image or live side is a list goes to k_ckpt_sub_rows (the check; in
-  // the write pass the live lists are dense, so only the image's lists do),
-  // every other to k_ckpt_sub.  Rows that subtract nothing leave the segments.
-  struct RowList {
-    std::vector<int32_t> row, form;
-    std::vector<uint64_t> off;
-    std::vector<uint32_t> m;
-    DevBuf d_row, d_form, d_off, d_m;
-    void push(int64_t r, const DirEntry& e, int depth) {
-      row.push_back((int32_t)r);
-      form.push_back(e.form == kRowHot ? 0 : table_form(e.form));
-      off.push_back(e.off);
-      m.push_back(e.form == kRowList ? (uint32_t)((e.len - 2) / (2 * (uint64_t)depth)) : 0u);
-    }
-    int upload(cms_handle* h) {
-      const size_t k = row.size();
-      if (k == 0) return CMS_OK;
-      CMS_HIP(d_row.ensure(sizeof(int32_t) * k));
-      CMS_HIP(d_form.ensure(sizeof(int32_t) * k));
-      CMS_HIP(d_off.ensure(sizeof(uint64_t) * k));
-      CMS_HIP(d_m.ensure(sizeof(uint32_t) * k));
-      CMS_HIP(hipMemcpyAsync(d_row.ptr, row.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, h->stream));
-      CMS_HIP(hipMemcpyAsync(d_form.ptr, form.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, h->stream));
-      CMS_HIP(hipMemcpyAsync(d_off.ptr, off.data(), sizeof(uint64_t) * k, hipMemcpyHostToDevice, h->stream));
-      CMS_HIP(hipMemcpyAsync(d_m.ptr, m.data(), sizeof(uint32_t) * k, hipMemcpyHostToDevice, h->stream));
-      return CMS_OK;
-    }
-  };
-  RowList crows, wrows;            // the check's and the write pass's listed rows
+  // The rows the image subtracts from, and which kernel takes each.  In the
+  // check a row whose image or live side is a list goes to k_ckpt_check_rows;
+  // in the write pass the live lists are dense, so only the image's lists go
+  // to k_ckpt_apply_lists; every other row to k_ckpt_apply.  Rows that
+  // subtract nothing leave the segments.
+  RowList crows;  // the check's listed rows
   std::vector<uint64_t> len_check(sg.len), len_write(sg.len);
-  std::vector<int64_t> touched;
-  std::vector<uint64_t> bound;     // a live list row's own mass: widen_rows rewrites it densely
   bool live_lists = false;
   for (size_t s = 0, r = 0; s < sg.len.size(); ++s, ++r) {
     while (im.dir[r].len == 0) ++r;
@@ -1720,118 +1631,95 @@ int subtract_resident(cms_handle* h, Image& im, const uint8_t* d_payload) {
     if (hidx[r] < 0 && off[r] == 0)  // (mass > 0 passed the mass rule, yet the owner has no counters)
       return set_error(CMS_E_STATE, "cms_subtract_table: owner row %lld has a mass and no counters", (long long)r);
     const bool live_list = hidx[r] == kFormList;
-    touched.push_back((int64_t)r);
+    job.touched.push_back((int64_t)r);
     if (img_list || live_list) {
       crows.push((int64_t)r, e, hd.depth);
       len_check[s] |= kListBit;
     }
     if (img_list) {
-      wrows.push((int64_t)r, e, hd.depth);
+      job.lists.push((int64_t)r, e, hd.depth);
       len_write[s] |= kListBit;
     }
-    if (live_list) {
-      if (bound.empty()) bound.assign((size_t)n, 0);
-      bound[r] = mass[r];
+    if (live_list) {  // the row's own mass: widen_rows rewrites it densely
+      if (job.bound.empty()) job.bound.assign((size_t)n, 0);
+      job.bound[r] = job.mass[r];
       live_lists = true;
     }
   }
-  unsigned long long res[3] = {0, 0, 0};
-  const size_t lds = 2 * (size_t)h->p.width;
-  auto launch = [&](bool write, RowList& rl) -> int {
-    if ((rc = rl.upload(h))) return rc;
-    TimedScope ts(h, write ? "ckpt_sub" : "ckpt_subcheck");
-    if (chunks > 0) {
-      if (write)
-        hipLaunchKernelGGL(k_ckpt_sub<true>, dim3(grid_for(h, chunks)), dim3(256), 0, h->stream, sg.view(), chunks, d_payload,
-                           h->tview(), d_out.as<unsigned long long>());
-      else
-        hipLaunchKernelGGL(k_ckpt_sub<false>, dim3(grid_for(h, chunks)), dim3(256), 0, h->stream, sg.view(), chunks, d_payload,
-                           h->tview(), d_out.as<unsigned long long>());
-    }
-    if (!rl.row.empty()) {
-      const dim3 g((unsigned)std::min<size_t>(rl.row.size(), 65536));
-      if (write)
-        hipLaunchKernelGGL(k_ckpt_sub_rows<true>, g, dim3(256), lds, h->stream, rl.d_row.as<int32_t>(), rl.d_off.as<uint64_t>(),
-                           rl.d_form.as<int32_t>(), rl.d_m.as<uint32_t>(), (int64_t)rl.row.size(), d_payload, h->tview(),
-                           (int)h->p.depth, d_out.as<unsigned long long>());
-      else
-        hipLaunchKernelGGL(k_ckpt_sub_rows<false>, g, dim3(256), lds, h->stream, rl.d_row.as<int32_t>(), rl.d_off.as<uint64_t>(),
-                           rl.d_form.as<int32_t>(), rl.d_m.as<uint32_t>(), (int64_t)rl.row.size(), d_payload, h->tview(),
-                           (int)h->p.depth, d_out.as<unsigned long long>());
-    }
-    CMS_HIP(hipGetLastError());
-    return CMS_OK;
-  };
   // ---- the counter check: no store ----
   sg.len = len_check;
   if ((rc = sg.upload(h))) return rc;
-  if ((rc = launch(false, crows))) return rc;
-  CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
-  CMS_HIP(hipStreamSynchronize(h->stream));
+  if ((rc = launch_apply(h, Apply::kCheck, job, crows, d_payload))) return rc;
+  unsigned long long res[3] = {0, 0, 0};
+  if ((rc = read_out(h, job, res))) return rc;
   if (res[1] & kBadDest) return set_error(CMS_E_STATE, "cms_subtract_table: a live row changed form under the call");
   if (res[1] & kBadUnder)
     return set_error(CMS_E_OVERFLOW, "owner row %lld: a counter would fall below zero (the image is no part of this table's stream)",
                      (long long)res[2]);
 
   // ---- every check has passed: the first write follows ----
-  DevBuf d_touched;
   if (live_lists) {  // bound > 0 on a list row is a rewrite (widen_needed); every other row's bound is 0: not listed
     CMS_HIP(h->ws_bound.ensure(sizeof(uint64_t) * (size_t)n));
-    CMS_HIP(hipMemcpyAsync(h->ws_bound.ptr, bound.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    CMS_HIP(hipMemcpyAsync(h->ws_bound.ptr, job.bound.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(k_ckpt_list_bounds, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192))),
                        dim3(256), 0, h->stream, h->ws_bound.as<uint64_t>(), h->d_cbound, n);
     CMS_HIP(hipGetLastError());
     if ((rc = widen_rows(h, h->ws_bound.as<uint64_t>(), nullptr, false))) return rc;
   }
-  if (h->rf_valid && !touched.empty()) {
-    CMS_HIP(d_touched.ensure(sizeof(int64_t) * touched.size()));
-    CMS_HIP(hipMemcpyAsync(d_touched.ptr, touched.data(), sizeof(int64_t) * touched.size(), hipMemcpyHostToDevice, h->stream));
-    if ((rc = refresh_mark(h, d_touched.as<int64_t>(), (int64_t)touched.size()))) return rc;
-  }
   sg.len = len_write;
-  if ((rc = sg.upload(h))) return rc;
-  if ((rc = launch(true, wrows))) return rc;
-  for (int64_t r = 0; r < n; ++r) mass[r] -= im.dir[r].mass;
-  CMS_HIP(hipMemcpyAsync(h->d_row_mass, mass.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
-  CMS_HIP(hipStreamSynchronize(h->stream));
-  h->pairs_ingested = h->pairs_ingested > hd.pairs_ingested ? h->pairs_ingested - hd.pairs_ingested : 0;
+  return sg.upload(h);
+}
+
+// The image (head parsed and validated into im, payload resident at d_payload,
+// 16-byte aligned) added into the live table, or subtracted from it (u32
+// counters).  Every check precedes the first write: a refusal leaves the table
+// as it was.
+int apply_resident(cms_handle* h, Apply op, Image& im, const uint8_t* d_payload) {
+  const Header& hd = im.hd;
+  const int64_t n = h->n;
+  const bool add = op == Apply::kAdd;
+  ApplyJob job;
+  int rc = apply_open(h, op, im, d_payload, job);
+  if (rc) return rc;
+  if (!add && h->empty) return CMS_OK;  // every mass of the image is zero: nothing to take out of no counters
+  if ((rc = add ? merge_prepare(h, im, job) : subtract_prepare(h, im, d_payload, job))) return rc;
+  if ((rc = mark_touched(h, job))) return rc;
+  if ((rc = launch_apply(h, op, job, job.lists, d_payload))) return rc;
+  for (int64_t r = 0; r < n; ++r)  // the true masses, not the bounds
+    job.mass[r] = add ? job.mass[r] + im.dir[r].mass : job.mass[r] - im.dir[r].mass;
+  CMS_HIP(hipMemcpyAsync(h->d_row_mass, job.mass.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  unsigned long long res[3] = {0, 0, 0};
+  if ((rc = read_out(h, job, res))) return rc;
+  // "ingested, not finalized", as after a COO batch; cms_finalize re-derives norms and row maxima
+  if (add) {
+    h->pairs_ingested += hd.pairs_ingested;
+    h->empty = false;
+  } else {
+    h->pairs_ingested = h->pairs_ingested > hd.pairs_ingested ? h->pairs_ingested - hd.pairs_ingested : 0;
+  }
   h->norms_valid = false;
   h->finalized = false;
   h->stale_possible = true;
-  if (res[1] & kBadDest) return set_error(CMS_E_STATE, "cms_subtract_table: a live row was in no form to give up its counters");
+  if (res[1] & kBadDest)
+    return set_error(CMS_E_STATE, add ? "cms_merge_table: a live row was in no form to take its adds"
+                                      : "cms_subtract_table: a live row was in no form to give up its counters");
   return CMS_OK;
 }
 
 // The file is staged whole in device memory (through two pinned buffers), then
 // merged (or subtracted) as a device image: the verify pass must see all of it before the
 // first write, and a list row may straddle any staging boundary.
-int merge_file(cms_handle* h, const char* path, bool subtract = false) {
+int merge_file(cms_handle* h, const char* path, Apply op) {
   File in;
-  in.f = std::fopen(path, "rb");
-  if (!in.f) return set_error(CMS_E_PARAM, "cannot open %s", path);
   Image im;
-  if (std::fseek(in.f, 0, SEEK_END) != 0) return set_error(CMS_E_PARAM, "cannot seek in %s", path);
-  const long long size = (long long)std::ftell(in.f);
-  std::rewind(in.f);
-  if (size < (long long)sizeof(Header) || std::fread(&im.hd, sizeof(Header), 1, in.f) != 1)
-    return set_error(CMS_E_PARAM, "checkpoint %s: shorter than a checkpoint header", path);
-  if (const char* why = check_header(im.hd, (uint64_t)size)) return set_error(CMS_E_PARAM, "checkpoint %s: %s", path, why);
-  int rc = check_matches(h, im.hd);
+  int rc = read_head_file(in, path, h, im);
   if (rc) return rc;
   const Header& hd = im.hd;
-  {
-    std::vector<uint8_t> head((size_t)hd.payload_off);
-    std::rewind(in.f);
-    if (std::fread(head.data(), 1, head.size(), in.f) != head.size())
-      return set_error(CMS_E_PARAM, "checkpoint %s: short read", path);
-    if ((rc = parse_head(head.data(), im))) return rc;
-  }
   DevBuf payload;
   if (payload.ensure((size_t)std::max<uint64_t>(hd.payload_bytes, 16)) != hipSuccess) {
     (void)hipGetLastError();
-    return set_error(CMS_E_OOM, "%s: no device memory to stage the %.2f GB image", subtract ? "cms_subtract_table" : "cms_merge_table",
-                     1e-9 * (double)hd.payload_bytes);
+    return set_error(CMS_E_OOM, "%s: no device memory to stage the %.2f GB image",
+                     op == Apply::kSub ? "cms_subtract_table" : "cms_merge_table", 1e-9 * (double)hd.payload_bytes);
   }
   const uint64_t nchunks = (hd.payload_bytes + kIoChunk - 1) / kIoChunk;
   if (nchunks > 0) {
@@ -1849,28 +1737,13 @@ int merge_file(cms_handle* h, const char* path, bool subtract = false) {
     CMS_HIP(hipStreamSynchronize(h->side_stream));
     add_host_time(h, "ckpt_io", t_io);
   }
-  return subtract ? subtract_resident(h, im, payload.as<uint8_t>()) : merge_resident(h, im, payload.as<uint8_t>());
+  return apply_resident(h, op, im, payload.as<uint8_t>());
 }
 
-int merge_device(cms_handle* h, const void* d_buf, int64_t bytes, bool subtract = false) {
-  if (bytes < (int64_t)sizeof(Header)) return set_error(CMS_E_PARAM, "checkpoint image: shorter than a checkpoint header");
-  if (reinterpret_cast<uintptr_t>(d_buf) & 15) return set_error(CMS_E_PARAM, "device image must be 16-byte aligned");
-  CMS_HIP(hipStreamSynchronize(h->stream));
+int merge_device(cms_handle* h, const void* d_buf, int64_t bytes, Apply op) {
   Image im;
-  CMS_HIP(hipMemcpy(&im.hd, d_buf, sizeof(Header), hipMemcpyDeviceToHost));
-  if (const char* why = check_header(im.hd, (uint64_t)bytes)) return set_error(CMS_E_PARAM, "checkpoint image: %s", why);
-  int rc = check_matches(h, im.hd);
-  if (rc) return rc;
-  const Header& hd = im.hd;
-  {
-    std::vector<uint8_t> head((size_t)hd.payload_off);
-    CMS_HIP(hipMemcpy(head.data(), d_buf, head.size(), hipMemcpyDeviceToHost));
-    if (std::memcmp(head.data(), &im.hd, sizeof(Header)) != 0)
-      return set_error(CMS_E_PARAM, "checkpoint image changed while it was read");
-    if ((rc = parse_head(head.data(), im))) return rc;
-  }
-  const uint8_t* d_payload = static_cast<const uint8_t*>(d_buf) + hd.payload_off;
-  return subtract ? subtract_resident(h, im, d_payload) : merge_resident(h, im, d_payload);
+  if (int rc = read_head_device(d_buf, bytes, h, im)) return rc;
+  return apply_resident(h, op, im, static_cast<const uint8_t*>(d_buf) + im.hd.payload_off);
 }
 
 // ---- compact ----
@@ -2115,16 +1988,6 @@ int fold_payload(cms_handle* h, int32_t wf, FoldPlan& fp, uint8_t* d_payload) {
   return CMS_OK;
 }
 
-// header, IDs (and the gap before the directory), directory: the image's first payload_off bytes
-std::vector<uint8_t> image_head(const Image& im) {
-  const Header& hd = im.hd;
-  std::vector<uint8_t> head((size_t)hd.payload_off, 0);
-  std::memcpy(head.data(), &hd, sizeof(hd));
-  if (!im.ids.empty()) std::memcpy(head.data() + hd.ids_off, im.ids.data(), (size_t)hd.ids_bytes);
-  std::memcpy(head.data() + hd.dir_off, im.dir.data(), (size_t)hd.dir_bytes);
-  return head;
-}
-
 int fold_device(cms_handle* h, int32_t wf, void* d_buf, int64_t capacity, int64_t* bytes) {
   FoldPlan fp;
   int rc = fold_plan(h, wf, fp);
@@ -2157,37 +2020,28 @@ int fold_file(cms_handle* h, int32_t wf, const char* path) {
     return set_error(CMS_E_OOM, "cms_fold_table: no device memory for the folded rows; nothing is written");
   }
   if ((rc = fold_payload(h, wf, fp, payload.as<uint8_t>()))) return rc;
-  const std::string tmp = std::string(path) + ".tmp";
-  TmpRemover cleanup{tmp};  // (declared before the file: it is closed first)
-  File out;
-  out.f = std::fopen(tmp.c_str(), "wb");
-  if (!out.f) return set_error(CMS_E_PARAM, "cannot open %s for writing", tmp.c_str());
-  const auto t_io = std::chrono::steady_clock::now();
-  const std::vector<uint8_t> head = image_head(fp.im);
-  bool ok = std::fwrite(head.data(), 1, head.size(), out.f) == head.size();
-  const uint64_t total = hd.payload_bytes, nchunks = (total + kIoChunk - 1) / kIoChunk;
-  if (ok && nchunks > 0) {
-    Staging st;
-    if ((rc = st.init(std::min(kIoChunk, total), false))) return rc;
-    auto span = [&](uint64_t i) { return std::min(total, (i + 1) * kIoChunk) - i * kIoChunk; };
-    for (uint64_t i = 0; i <= nchunks && ok; ++i) {  // D2H of chunk i while the host writes chunk i - 1
-      if (i < nchunks) {
-        CMS_HIP(hipMemcpyAsync(st.pin[i & 1], payload.as<uint8_t>() + i * kIoChunk, (size_t)span(i), hipMemcpyDeviceToHost,
-                               h->stream));
-        CMS_HIP(hipEventRecord(st.ev_a[i & 1], h->stream));
-      }
-      if (i >= 1) {
-        CMS_HIP(hipEventSynchronize(st.ev_a[(i - 1) & 1]));
-        ok = std::fwrite(st.pin[(i - 1) & 1], 1, (size_t)span(i - 1), out.f) == span(i - 1);
+  return write_atomically(h, path, [&](FILE* f, bool& ok) -> int {
+    const std::vector<uint8_t> head = image_head(fp.im);
+    ok = std::fwrite(head.data(), 1, head.size(), f) == head.size();
+    const uint64_t total = hd.payload_bytes, nchunks = (total + kIoChunk - 1) / kIoChunk;
+    if (ok && nchunks > 0) {
+      Staging st;
+      if (int r = st.init(std::min(kIoChunk, total), false)) return r;
+      auto span = [&](uint64_t i) { return std::min(total, (i + 1) * kIoChunk) - i * kIoChunk; };
+      for (uint64_t i = 0; i <= nchunks && ok; ++i) {  // D2H of chunk i while the host writes chunk i - 1
+        if (i < nchunks) {
+          CMS_HIP(hipMemcpyAsync(st.pin[i & 1], payload.as<uint8_t>() + i * kIoChunk, (size_t)span(i), hipMemcpyDeviceToHost,
+                                 h->stream));
+          CMS_HIP(hipEventRecord(st.ev_a[i & 1], h->stream));
+        }
+        if (i >= 1) {
+          CMS_HIP(hipEventSynchronize(st.ev_a[(i - 1) & 1]));
+          ok = std::fwrite(st.pin[(i - 1) & 1], 1, (size_t)span(i - 1), f) == span(i - 1);
+        }
       }
     }
-  }
-  const bool closed = std::fclose(out.f) == 0;
-  out.f = nullptr;
-  add_host_time(h, "ckpt_io", t_io);
-  if (!ok || !closed) return set_error(CMS_E_PARAM, "short write to %s", tmp.c_str());
-  if (std::rename(tmp.c_str(), path) != 0) return set_error(CMS_E_PARAM, "cannot rename %s to %s", tmp.c_str(), path);
-  return CMS_OK;
+    return CMS_OK;
+  });
 }
 
 // what a fold accepts: what a save accepts, of u32 counters
@@ -2246,7 +2100,7 @@ int cms_merge_table(cms_handle* h, const char* path) {
   if (int rc = cms_synchronize(h)) return rc;  // a pending device-ingest error comes first: nothing is merged
   Guard g(h);
   if (int rc = check_receives_image(h, "cms_merge_table")) return rc;
-  return merge_file(h, path);
+  return merge_file(h, path, Apply::kAdd);
 }
 
 int cms_merge_table_device(cms_handle* h, const void* d_buf, int64_t bytes) {
@@ -2254,7 +2108,7 @@ int cms_merge_table_device(cms_handle* h, const void* d_buf, int64_t bytes) {
   if (int rc = cms_synchronize(h)) return rc;
   Guard g(h);
   if (int rc = check_receives_image(h, "cms_merge_table_device")) return rc;
-  return merge_device(h, d_buf, bytes);
+  return merge_device(h, d_buf, bytes, Apply::kAdd);
 }
 
 // (an fp64 subtraction is no inverse of the reference's rounded adds)
@@ -2271,7 +2125,7 @@ int cms_subtract_table(cms_handle* h, const char* path) {
   if (int rc = cms_synchronize(h)) return rc;  // a pending device-ingest error comes first: nothing is subtracted
   Guard g(h);
   if (int rc = check_subtracts(h, "cms_subtract_table")) return rc;
-  return merge_file(h, path, true);
+  return merge_file(h, path, Apply::kSub);
 }
 
 int cms_subtract_table_device(cms_handle* h, const void* d_buf, int64_t bytes) {
@@ -2279,7 +2133,7 @@ int cms_subtract_table_device(cms_handle* h, const void* d_buf, int64_t bytes) {
   if (int rc = cms_synchronize(h)) return rc;
   Guard g(h);
   if (int rc = check_subtracts(h, "cms_subtract_table_device")) return rc;
-  return merge_device(h, d_buf, bytes, true);
+  return merge_device(h, d_buf, bytes, Apply::kSub);
 }
 
 int cms_compact_table(cms_handle* h, int64_t* rows_changed) {
@@ -2328,15 +2182,8 @@ int cms_fold_table_device(cms_handle* h, int32_t new_width, void* d_buf, int64_t
 int cms_checkpoint_info(const char* path, cms_params* out, int64_t* file_bytes) {
   if (!path || !out) return set_error(CMS_E_PARAM, "null argument");
   File in;
-  in.f = std::fopen(path, "rb");
-  if (!in.f) return set_error(CMS_E_PARAM, "cannot open %s", path);
   Header hd;
-  if (std::fseek(in.f, 0, SEEK_END) != 0) return set_error(CMS_E_PARAM, "cannot seek in %s", path);
-  const long long size = (long long)std::ftell(in.f);
-  std::rewind(in.f);
-  if (size < (long long)sizeof(Header) || std::fread(&hd, sizeof(Header), 1, in.f) != 1)
-    return set_error(CMS_E_PARAM, "checkpoint %s: shorter than a checkpoint header", path);
-  if (const char* why = check_header(hd, (uint64_t)size)) return set_error(CMS_E_PARAM, "checkpoint %s: %s", path, why);
+  if (int rc = read_header_file(in, path, hd)) return rc;
   std::memset(out, 0, sizeof(*out));
   out->struct_size = sizeof(cms_params);
   out->depth = hd.depth;

@@ -11,7 +11,9 @@ memory-bound yardstick taken in the same process:
                         without a merge: the same 20 batches re-ingested into
                         a restored copy of the live table
 
-  ckpt_verify / ckpt_add  the library's timing scopes (kernel time)
+  ckpt_verify / ckpt_add  the library's timing scopes (kernel time):
+                          k_ckpt_unpack<false>; k_ckpt_apply<kAdd> and
+                          k_ckpt_apply_lists<kAdd>
   yardstick               a device-to-device copy of the image's bytes plus a
                           read-and-write pass over as many bytes as the live
                           table stores after the merge (the rows it touched)

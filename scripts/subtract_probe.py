@@ -11,7 +11,9 @@ in the same process:
                         streams at once, list rows and all, loses the second
 
   ckpt_verify / ckpt_subcheck / ckpt_sub / widen_rows   the library's timing
-                        scopes (kernel time) of the subtraction
+                        scopes (kernel time) of the subtraction: ckpt_subcheck
+                        is k_ckpt_apply<kCheck> and k_ckpt_check_rows,
+                        ckpt_sub k_ckpt_apply<kSub> and k_ckpt_apply_lists<kSub>
   (a) memory-bound      a device-to-device copy of the image's bytes plus a
                         read-and-write pass over the live table's stored bytes
                         (ckpt_sub); the copy plus a read pass over them

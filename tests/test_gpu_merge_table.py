@@ -1,6 +1,6 @@
 """GPU: a saved sketch table merged into a live one (cms_merge_table /
-cms_merge_table_device: k_ckpt_unpack's verify pass, then k_ckpt_add and
-k_ckpt_add_lists after the in-place writers' promote / widen step).  Every
+cms_merge_table_device: k_ckpt_unpack's verify pass, then k_ckpt_apply<kAdd>
+and k_ckpt_apply_lists<kAdd> after the in-place writers' promote / widen step).  Every
 comparison covers the WHOLE table and is bit for bit against the oracle's
 rebuild of both streams (`T/impl/common/DoubleCountMinSketch.java:72-80`) and
 against the numpy specification checkpoint.sum_counters.
@@ -687,3 +687,136 @@ def test_default_file_merges_into_every_layout(oracle, tmp_path, monkeypatch, va
         sims = oracle.similarities_row(both, 1)
         sims[1] = oracle.cosine_cm(both[1], both[1])
         assert _same(b.similarities(1, np.arange(n)), sims)
+
+
+# ---- 9: designed images: a long list in one bucket; the one group below a byte ----
+
+def _device(t, data):
+    import torch
+    return torch.frombuffer(bytearray(data), dtype=torch.uint8).to(torch.device("cuda", t.device))
+
+
+def _narrowest(bound, w):
+    """widen_target for a row without counters of its own (cms_forms.h)."""
+    if bound <= 1 and w % 128 == 0:
+        return "u1"
+    if bound <= 3 and w % 64 == 0:
+        return "u2"
+    return "u4" if bound <= 15 else "u8" if bound <= 255 else "u16"
+
+
+def _masses(t, tmp_path):
+    path = str(tmp_path / "masses.ckpt")
+    t.save(path)
+    return ck.read_checkpoint(path).masses
+
+
+# (m, w): the loader takes a list only while it is shorter than the u16 row (2 + 2 d m <= 2 d w), so at d = 2 the
+# longest list a build stores, m = 1024, needs w > 1024; 511 is the longest at w = 512
+LONG_LISTS = [(255, 512), (256, 512), (300, 512), (511, 512), (1024, 2048)]
+
+
+@pytest.mark.parametrize("m,w", LONG_LISTS)
+def test_a_long_list_in_one_bucket(oracle, tmp_path, m, w):
+    """Image row 0 is a list of m entries that all share bucket 5 of sketch row
+    0 and bucket 7 of sketch row 1: the loader bounds a list's length, not a
+    bucket's count, so a count passes 2^8.  (A u8 cell, four to a word, would
+    carry from bucket 5 into bucket 6 and off the word from bucket 7.)  Merged
+    into an empty table, a u8 row, a u32 row and a list row, every counter of
+    every row is live + image, row 0 in the narrowest form that holds its
+    bound; the subtraction of the same image gives the live table back.
+
+    On the commit before the list rows' write pass counted in u16 cells (and
+    before merge_increment bounded a list's counter by 1024, not 255) this test
+    passed for m = 255 and failed for every longer list, with wrong counters
+    and nothing worse.  Into the empty table, sketch row 0 / buckets 5 and 6,
+    sketch row 1 / bucket 7: m = 256 gave 0, 1, 0; m = 300 gave 44, 1, 44;
+    m = 511 gave 255, 1, 255; m = 1024 gave 0, 4, 0 -- m mod 256 in the bucket,
+    the carry in bucket 6, and off the top of the word from bucket 7."""
+    n, d = 4, 2
+    ha, hb = oracle.hash_params(42, d)
+    forms, _ = _layout(w)
+    img = np.zeros((n, d, w), np.uint64)
+    img[0, 0, 5] = img[0, 1, 7] = m
+    img[1, :, 3:9] = 2
+    img[2, 1, 100] = 70000  # a u32 image row
+    img[3, 0, w - 1] = 1
+    image = ck.build_checkpoint(img, ha, hb, seed=42, lists={0: np.array([[5] * m, [7] * m])})
+    assert ck.ROW_FORMS[ck.Checkpoint(image).forms[0]] == "list"
+    lives = {}
+    lives["empty"] = None
+    c = np.zeros((n, d, w), np.uint64)
+    c[0, :, 5], c[0, :, 6], c[0, :, 7] = 3, 200, 1
+    c[1, 0, 4] = 9
+    lives["u8"] = (c, dict(forms=["u8", None, None, None]))
+    c = np.zeros((n, d, w), np.uint64)
+    c[0, :, 5], c[0, :, 6], c[0, :, 7] = 70000, 3 * 65535, 255
+    c[3, :, w - 1] = 14
+    lives["u32"] = (c, dict(forms=["u32", None, None, None]))
+    c = np.zeros((n, d, w), np.uint64)
+    c[0, :, 5] = c[0, :, 6] = c[0, :, 7] = 1
+    c[2, 0, 100] = 5
+    lives["list"] = (c, dict(lists={0: np.array([[5, 6, 7], [5, 6, 7]])}))
+    for name, live in lives.items():
+        with SketchTable(n, depth=d, width=w, seed=42) as t:
+            if live is None:
+                base = np.zeros((n, d, w), np.uint64)
+            else:
+                base = live[0]
+                t.load_device(_device(t, ck.build_checkpoint(base, ha, hb, seed=42, **live[1])))
+                assert not forms or FORMS[t.owner_forms()[0][0]] == name
+            mass0 = _masses(t, tmp_path) if live is not None else np.zeros(n, np.uint64)
+            dev = _device(t, image)
+            t.merge_device(dev)
+            got = t.read_counters()
+            print(name, m, "row 0 buckets 4..8:", got[0, :, 4:9].tolist())
+            assert np.array_equal(got, (base + img).astype(np.float64)), (name, m)
+            # (the u8 row's mass is 204: with m more it passes u8 for every m here)
+            want = "u32" if name == "u32" else _narrowest(int(mass0[0]) + m, w) if forms else "u16"
+            assert FORMS[t.owner_forms()[0][0]] == want, (name, m, FORMS[t.owner_forms()[0][0]], want)
+            assert np.array_equal(_masses(t, tmp_path), mass0 + ck.Checkpoint(image).masses)
+            t.subtract_device(dev)
+            assert np.array_equal(t.read_counters(), base.astype(np.float64)), (name, m)
+            assert np.array_equal(_masses(t, tmp_path), mass0)
+
+
+def test_u32_image_counters_out_of_a_one_bit_row(oracle, tmp_path):
+    """The one group below a byte: four u32 image counters face four bits of a
+    1-bit live row, the low or the high half of a byte that the neighbouring
+    lane's chunk shares."""
+    n, d, w = 4, 2, 512
+    ha, hb = oracle.hash_params(42, d)
+    live = np.zeros((n, d, w), np.uint64)
+    live[1, 0, 0:8] = 1       # both halves of byte 0 of sketch row 0
+    live[1, 1, 40:48] = 1     # and of byte 5 of sketch row 1
+    live[1, 1, 509] = 1
+    live[2, :, 7] = 3
+    img = np.zeros((n, d, w), np.uint64)
+    img[1, 0, [0, 1, 6, 7]] = 1
+    img[1, 1, [41, 42, 44, 509]] = 1
+
+    def image_of(c):
+        return ck.build_checkpoint(c, ha, hb, seed=42, forms=[None, "u32", None, None])
+
+    with SketchTable(n, depth=d, width=w, seed=42) as t:
+        t.load_device(_device(t, ck.build_checkpoint(live, ha, hb, seed=42, forms=[None, "u1", None, None])))
+        assert not _layout(w)[0] or FORMS[t.owner_forms()[0][1]] == "u1"
+        dev = _device(t, image_of(img))
+        t.subtract_device(dev)
+        left = live - img
+        assert np.array_equal(t.read_counters(), left.astype(np.float64))
+        assert not _layout(w)[0] or FORMS[t.owner_forms()[0][1]] == "u1"
+        assert int(_masses(t, tmp_path)[1]) == 5
+        snap = _snapshot(t)
+        with pytest.raises(_lib.CmsError) as ei:  # the masses allow it (5 >= 4), the counters do not
+            t.subtract_device(dev)
+        assert ei.value.code == _lib.CMS_E_OVERFLOW and "owner row 1" in str(ei.value), str(ei.value)
+        assert _unchanged(t, snap)
+        # bucket 2 (low half) is still set, bucket 6 (high half) no longer: the compare looks at the right half
+        one = np.zeros((n, d, w), np.uint64)
+        one[1, 0, [2, 6]] = 1
+        assert _code(t.subtract_device, _device(t, image_of(one))) == _lib.CMS_E_OVERFLOW
+        assert _unchanged(t, snap)
+        one[1, 0, 6], one[1, 0, 5] = 0, 1  # buckets 2 and 5: both set
+        t.subtract_device(_device(t, image_of(one)))
+        assert np.array_equal(t.read_counters(), (left - one).astype(np.float64))

@@ -1,7 +1,8 @@
 """GPU: a saved sketch table subtracted from a live one (cms_subtract_table /
 cms_subtract_table_device: k_ckpt_unpack's verify pass, the counter check of
-k_ckpt_sub<false> and k_ckpt_sub_rows<false>, then widen_rows over the live
-list rows and the subtraction itself).  Every comparison covers the WHOLE
+k_ckpt_apply<kCheck> and k_ckpt_check_rows, then widen_rows over the live
+list rows and the subtraction itself, k_ckpt_apply<kSub> and
+k_ckpt_apply_lists<kSub>).  Every comparison covers the WHOLE
 table and is bit for bit against the oracle's rebuild of the remaining stream
 (`T/impl/common/DoubleCountMinSketch.java:72-80`) and against the numpy
 specification checkpoint.diff_counters.

@@ -151,6 +151,8 @@ def test_an_empty_live_table_and_fp64_counters(shim):
     ("list", 2, 0, 0, 0),            # a list of no entries
     ("list", 2 + 8 * 5, 2, 5, 2),    # min(cbound, mass)
     ("list", 2 + 8 * 5, 9, 5, 5),
+    ("list", 2 + 8 * 300, 300, 300, 300),    # every key in one bucket: the loader bounds the length, not a bucket
+    ("list", 2 + 8 * 1024, 0, 2000, 1024),   # no cbound: the longest list there is
     ("u1", 64, 1, 40, 1),
     ("u2", 128, 3, 2, 2),
     ("u4", 256, 9, 1000, 9),
