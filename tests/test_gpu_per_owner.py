@@ -289,7 +289,8 @@ def test_big_queries_and_full_classes(oracle):
                 else:
                     os.environ[kk] = v
 
-    shapes, (ids, sc, cnt), rows = run({})
+    # (the baseline pins both switches: it asserts that pruning happened, whatever the caller's environment)
+    shapes, (ids, sc, cnt), rows = run({"CMS_PO_NO_PRUNE": "0", "CMS_PO_NO_BIGQ": "0"})
     w, d = shapes
     cls = {}
     for r in range(n):
@@ -297,10 +298,10 @@ def test_big_queries_and_full_classes(oracle):
     assert max(len(v) for v in cls.values()) > 64
     wide_pairs, wide_exact = run.pruned
     assert wide_pairs > 0 and wide_exact < wide_pairs  # the row-0 bound ruled wide pairs out
-    _, (ids2, sc2, cnt2), _ = run({"CMS_PO_NO_BIGQ": "1"})
+    _, (ids2, sc2, cnt2), _ = run({"CMS_PO_NO_BIGQ": "1", "CMS_PO_NO_PRUNE": "0"})
     assert np.array_equal(cnt, cnt2) and np.array_equal(ids, ids2) and same(sc, sc2)
     # every (query, wide owner) pair computed exactly: the same lists
-    _, (ids3, sc3, cnt3), _ = run({"CMS_PO_NO_PRUNE": "1"})
+    _, (ids3, sc3, cnt3), _ = run({"CMS_PO_NO_PRUNE": "1", "CMS_PO_NO_BIGQ": "0"})
     assert run.pruned == (0, 0)
     assert np.array_equal(cnt, cnt3) and np.array_equal(ids, ids3) and same(sc, sc3)
     for q, row in rows.items():

@@ -29,8 +29,11 @@ def _same(x, y):
     return x.shape == y.shape and bool(np.all((x == y) | (np.isnan(x) & np.isnan(y))))
 
 
-def test_config2_per_owner_all_pairs_rows_equal_oracle(oracle):
+def test_config2_per_owner_all_pairs_rows_equal_oracle(oracle, monkeypatch):
     import torch
+    # the job under test is the pruned one with the big-query kernel, whatever the caller's environment
+    monkeypatch.setenv("CMS_PO_NO_PRUNE", "0")
+    monkeypatch.setenv("CMS_PO_NO_BIGQ", "0")
     from mahout_amd import SketchTable
     from mahout_amd.synth import zipf_stream_torch
     items, users = zipf_stream_torch(N_USERS, N_ITEMS, PAIRS, seed=SEED_STREAM, device="cuda")
