@@ -328,6 +328,46 @@ int cms_recommend_batch(cms_handle* h, int64_t n, const int64_t* user_ids, const
                         const int64_t* pref_offsets, const int64_t* pref_items, int32_t how_many,
                         int32_t include_known, int32_t use_capper, float cap_min, float cap_max, int32_t* out_counts,
                         int64_t* out_items, float* out_values);
+
+/* ---- item-based recommender: blocks of the similarity matrix -------------
+ * Fixed-shape u32 handles, after cms_finalize; a per-owner-shape or fp64
+ * handle is CMS_E_STATE.  The calls read the table as cms_similarities does
+ * (concurrent readers, nothing is changed).  With timing on they run on the
+ * handle's stream under the scopes "item_block" / "item_estimate".
+ *
+ * out[i * n2 + j] = userSimilarity(ids1[i], ids2[j]): row i equals
+ * cms_similarities(h, ids1[i], ids2, n2, .) bit for bit.  IDs may repeat.  An
+ * unknown ID is CMS_E_NO_SUCH_ID and nothing is written.  One workgroup per
+ * ids1[i] images that owner's sketch row in LDS once for all of ids2 (widths
+ * above 8192 go pair by pair through the kernel of cms_similarities). */
+int cms_similarity_block(cms_handle* h, const int64_t* ids1, int64_t n1, const int64_t* ids2, int64_t n2, double* out);
+/* GenericItemBasedRecommender.doEstimatePreference (:231-259) for n users
+ * over a handle whose owners are ITEMS: user u's preferences are pref_items /
+ * pref_vals [pref_offsets[u], pref_offsets[u + 1]) in PreferenceArray order,
+ * its candidates cand_items [cand_offsets[u], cand_offsets[u + 1]); out
+ * (floats) is parallel to cand_items.  Per candidate: the similarities with
+ * the preferred items, NaN skipped, preference += sim * pref and total += sim
+ * in preference order, NaN for fewer than two, (float)(preference / total),
+ * then the EstimatedPreferenceCapper clamp when use_capper.  Both offset arrays
+ * hold n + 1 non-decreasing entries from 0. */
+int cms_item_estimates_batch(cms_handle* h, int64_t n, const int64_t* pref_offsets, const int64_t* pref_items,
+                             const float* pref_vals, const int64_t* cand_offsets, const int64_t* cand_items,
+                             int32_t use_capper, float cap_min, float cap_max, float* out);
+/* GenericItemBasedRecommender.recommend(userID, howMany, null, includeKnownItems)
+ * (:120-139) for n users of the DataModel given as a CSR (model_user_ids
+ * strictly ascending; row r holds pref_items / pref_vals [pref_offsets[r],
+ * pref_offsets[r + 1])), over a handle whose owners are the model's items.
+ * strategy 0: PreferredItemsNeighborhoodCandidateItemsStrategy (the default),
+ * 1: AllUnknownItemsCandidateItemsStrategy.  The candidates come in FastIDSet
+ * iteration order, every estimate from one device batch, the ranking is
+ * TopItems.getTopItems with the JDK heap order.  out_counts[n] (0 for a user
+ * without preferences), out_items / out_values [n][how_many].  A user missing
+ * from the model is CMS_E_NO_SUCH_ID. */
+int cms_item_recommend_batch(cms_handle* h, int64_t n, const int64_t* user_ids, int64_t n_model_users,
+                             const int64_t* model_user_ids, const int64_t* pref_offsets, const int64_t* pref_items,
+                             const float* pref_vals, int32_t strategy, int32_t how_many, int32_t include_known,
+                             int32_t use_capper, float cap_min, float cap_max, int32_t* out_counts, int64_t* out_items,
+                             float* out_values);
 /* GenericUserBasedRecommender.mostSimilarUserIDs(id, k) with the CosineCM
  * estimator (:119-127, :231-247) and TopItems.getTopUsers (TopItems.java:91-136):
  * the first k other owners under (similarity desc, ID asc), NaN excluded.

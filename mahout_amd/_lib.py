@@ -55,6 +55,7 @@ EXPORTS = [
     "cms_compact_table",
     "cms_fold_size", "cms_fold_table", "cms_fold_table_device",
     "cms_threshold_neighbors", "cms_fastidset_to_array",
+    "cms_similarity_block", "cms_item_estimates_batch", "cms_item_recommend_batch",
 ]
 
 
@@ -198,6 +199,10 @@ _SIGS = {
     "cms_anonymous_batch": (_int, [_vp, _i32, ctypes.POINTER(_i32)]),
     "cms_threshold_neighbors": (_int, [_vp, _vp, _i64, _dbl, _i32, _vp, _vp, _vp, _i64, ctypes.POINTER(_i64)]),
     "cms_fastidset_to_array": (_int, [_vp, _i64, _vp, ctypes.POINTER(_i64)]),
+    "cms_similarity_block": (_int, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "cms_item_estimates_batch": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_float, ctypes.c_float, _vp]),
+    "cms_item_recommend_batch": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
+                                        ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
 }
 
 _lib = None

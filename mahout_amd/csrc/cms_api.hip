@@ -1295,6 +1295,148 @@ int cms_recommend_batch(cms_handle* h, int64_t n, const int64_t* user_ids, const
   return CMS_OK;
 }
 
+// ---- item-based recommender (cms_item.hip): similarity blocks, batched estimates ----
+
+static int item_require(cms_handle* h, const char* what) {
+  if (h->per_owner)
+    return set_error(CMS_E_STATE, "%s: not available on a per-owner-shape handle (cms_create_per_owner)", what);
+  if (h->f64) return set_error(CMS_E_STATE, "%s: not available on an fp64-counter handle (CMS_COUNTER_F64)", what);
+  return require_finalized(h);
+}
+
+// f(ctx, stream, timed) on the reader path of cms_similarities -- shared
+// guard, a leased stream and scratch -- unless timing is on: the scopes
+// (item_block, item_estimate) belong to the handle's stream, so a timed call
+// runs there, alone.
+extern "C++" {
+template <class F>
+static int item_reader(cms_handle* h, const char* what, F&& f) {
+  {
+    SharedGuard g(h);
+    if (int rc = item_require(h, what)) return rc;
+    if (h->timing == 0) {
+      CtxLease L(h);
+      if (int rc = L.ready()) return rc;
+      return f(*L.c, L.c->stream, false);
+    }
+  }
+  Guard g(h);
+  if (int rc = item_require(h, what)) return rc;
+  QueryCtx tmp;  // the handle's stream, call-local scratch
+  return f(tmp, h->stream, true);
+}
+}  // extern "C++"
+
+static int check_offsets(const char* name, const int64_t* off, int64_t n) {
+  if (off[0] != 0) return set_error(CMS_E_PARAM, "%s must start at 0", name);
+  for (int64_t u = 0; u < n; ++u)
+    if (off[u + 1] < off[u]) return set_error(CMS_E_PARAM, "%s must not decrease", name);
+  return CMS_OK;
+}
+
+int cms_similarity_block(cms_handle* h, const int64_t* ids1, int64_t n1, const int64_t* ids2, int64_t n2, double* out) {
+  if (!h || n1 < 0 || n2 < 0 || (n1 > 0 && !ids1) || (n2 > 0 && !ids2) || (n1 > 0 && n2 > 0 && !out))
+    return set_error(CMS_E_PARAM, "null argument");
+  return item_reader(h, "cms_similarity_block", [&](QueryCtx& c, hipStream_t st, bool timed) -> int {
+    std::vector<int64_t> left((size_t)n1), right((size_t)n2);
+    int rc;
+    for (int64_t i = 0; i < n1; ++i)
+      if ((rc = row_of(h, ids1[i], &left[(size_t)i]))) return rc;
+    for (int64_t i = 0; i < n2; ++i)
+      if ((rc = row_of(h, ids2[i], &right[(size_t)i]))) return rc;
+    return item_block(h, c, st, timed, left.data(), n1, right.data(), n2, out);
+  });
+}
+
+int cms_item_estimates_batch(cms_handle* h, int64_t n, const int64_t* pref_offsets, const int64_t* pref_items,
+                             const float* pref_vals, const int64_t* cand_offsets, const int64_t* cand_items,
+                             int32_t use_capper, float cap_min, float cap_max, float* out) {
+  if (!h || n < 0 || (n > 0 && (!pref_offsets || !cand_offsets))) return set_error(CMS_E_PARAM, "null argument");
+  if (n == 0) return CMS_OK;
+  if (int rc = check_offsets("pref_offsets", pref_offsets, n)) return rc;
+  if (int rc = check_offsets("cand_offsets", cand_offsets, n)) return rc;
+  const int64_t M = pref_offsets[n], Q = cand_offsets[n];
+  if ((M > 0 && (!pref_items || !pref_vals)) || (Q > 0 && (!cand_items || !out)))
+    return set_error(CMS_E_PARAM, "null argument");
+  if (Q >= (int64_t(1) << 31)) return set_error(CMS_E_PARAM, "too many candidate items in one batch");
+  return item_reader(h, "cms_item_estimates_batch", [&](QueryCtx& c, hipStream_t st, bool timed) -> int {
+    std::vector<int64_t> prows((size_t)M), crows((size_t)Q);
+    int rc;
+    for (int64_t i = 0; i < M; ++i)
+      if ((rc = row_of(h, pref_items[i], &prows[(size_t)i]))) return rc;
+    for (int64_t i = 0; i < Q; ++i)
+      if ((rc = row_of(h, cand_items[i], &crows[(size_t)i]))) return rc;
+    return item_estimates(h, c, st, timed, n, pref_offsets, prows.data(), pref_vals, cand_offsets, crows.data(),
+                          use_capper, cap_min, cap_max, out);
+  });
+}
+
+int cms_item_recommend_batch(cms_handle* h, int64_t n, const int64_t* user_ids, int64_t n_model_users,
+                             const int64_t* model_user_ids, const int64_t* pref_offsets, const int64_t* pref_items,
+                             const float* pref_vals, int32_t strategy, int32_t how_many, int32_t include_known,
+                             int32_t use_capper, float cap_min, float cap_max, int32_t* out_counts, int64_t* out_items,
+                             float* out_values) {
+  if (!h || n < 0 || n_model_users < 0 || (n > 0 && (!user_ids || !out_counts || !out_items || !out_values)) ||
+      (n_model_users > 0 && (!model_user_ids || !pref_offsets)))
+    return set_error(CMS_E_PARAM, "null argument");
+  if (how_many < 1) return set_error(CMS_E_PARAM, "howMany must be at least 1");
+  if (strategy != 0 && strategy != 1)
+    return set_error(CMS_E_PARAM, "strategy must be 0 (preferred items' neighbourhood) or 1 (all unknown items)");
+  if (n_model_users > 0) {
+    if (int rc = check_offsets("pref_offsets", pref_offsets, n_model_users)) return rc;
+    for (int64_t r = 1; r < n_model_users; ++r)
+      if (model_user_ids[r] <= model_user_ids[r - 1])
+        return set_error(CMS_E_PARAM, "model_user_ids must be strictly ascending");
+    if (pref_offsets[n_model_users] > 0 && (!pref_items || !pref_vals)) return set_error(CMS_E_PARAM, "null argument");
+  }
+  {
+    SharedGuard g(h);  // (the state errors before any host work)
+    if (int rc = item_require(h, "cms_item_recommend_batch")) return rc;
+  }
+  if (n == 0) return CMS_OK;
+  std::vector<int64_t> urow((size_t)n);
+  for (int64_t u = 0; u < n; ++u) {
+    const int64_t* it = std::lower_bound(model_user_ids, model_user_ids + n_model_users, user_ids[u]);
+    if (it == model_user_ids + n_model_users || *it != user_ids[u])
+      return set_error(CMS_E_NO_SUCH_ID, "no such user ID %lld in the data model", (long long)user_ids[u]);
+    urow[(size_t)u] = it - model_user_ids;
+  }
+  // candidates per user (host threads), in FastIDSet iteration order
+  ItemCandidates model(n_model_users, pref_offsets, pref_items);
+  std::vector<std::vector<int64_t>> cand((size_t)n);
+  const int threads = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
+  parallel_users(n, threads, [&](int64_t u) {
+    const int64_t r = urow[(size_t)u], m = pref_offsets[r + 1] - pref_offsets[r];
+    if (m == 0) return;  // recommend(): a user without preferences is recommended nothing
+    model.candidates(pref_items + pref_offsets[r], m, strategy, include_known != 0, cand[(size_t)u]);
+  });
+  // the users' preferences and candidates as one batch
+  std::vector<int64_t> p_off((size_t)n + 1, 0), c_off((size_t)n + 1, 0);
+  for (int64_t u = 0; u < n; ++u) {
+    const int64_t r = urow[(size_t)u];
+    p_off[(size_t)u + 1] = p_off[(size_t)u] + (pref_offsets[r + 1] - pref_offsets[r]);
+    c_off[(size_t)u + 1] = c_off[(size_t)u] + (int64_t)cand[(size_t)u].size();
+  }
+  std::vector<int64_t> p_items((size_t)p_off[(size_t)n]), c_items((size_t)c_off[(size_t)n]);
+  std::vector<float> p_vals(p_items.size());
+  for (int64_t u = 0; u < n; ++u) {
+    const int64_t r = urow[(size_t)u];
+    std::copy(pref_items + pref_offsets[r], pref_items + pref_offsets[r + 1], p_items.begin() + p_off[(size_t)u]);
+    std::copy(pref_vals + pref_offsets[r], pref_vals + pref_offsets[r + 1], p_vals.begin() + p_off[(size_t)u]);
+    std::copy(cand[(size_t)u].begin(), cand[(size_t)u].end(), c_items.begin() + c_off[(size_t)u]);
+  }
+  std::vector<float> est(c_items.size());
+  if (int rc = cms_item_estimates_batch(h, n, p_off.data(), p_items.data(), p_vals.data(), c_off.data(), c_items.data(),
+                                        use_capper, cap_min, cap_max, est.data()))
+    return rc;
+  parallel_users(n, threads, [&](int64_t u) {
+    const int64_t o = c_off[(size_t)u];
+    out_counts[u] = recommend_top_items(how_many, c_items.data() + o, est.data() + o, c_off[(size_t)u + 1] - o,
+                                        out_items + u * (int64_t)how_many, out_values + u * (int64_t)how_many);
+  });
+  return CMS_OK;
+}
+
 int cms_point_query(cms_handle* h, int64_t id, int64_t key, double* out) {
   if (!h || !out) return set_error(CMS_E_PARAM, "null argument");
   SharedGuard g(h);

@@ -740,6 +740,46 @@ int64_t fastidset_to_array(const int64_t* ids, int64_t n, int64_t* out);
 int32_t recommend_top_items(int32_t how_many, const int64_t* items, const float* est, int64_t q, int64_t* out_items,
                             float* out_values);
 void parallel_users(int64_t n, int threads, const std::function<void(int64_t)>& fn);
+// GenericItemBasedRecommender's candidate strategies over the user CSR
+// (model row r's item IDs pref_items[pref_offsets[r] .. pref_offsets[r + 1]),
+// which must outlive the object): the item side is the CSR transposed, raters
+// in ascending model row.  candidates() may run on many threads at once.
+struct ItemCandidatesImpl;
+class ItemCandidates {
+ public:
+  ItemCandidates(int64_t n_users, const int64_t* pref_offsets, const int64_t* pref_items);
+  ~ItemCandidates();
+  ItemCandidates(const ItemCandidates&) = delete;
+  ItemCandidates& operator=(const ItemCandidates&) = delete;
+  // getItemIDs(): ascending
+  const std::vector<int64_t>& item_ids() const;
+  // getPreferencesForItem(item): the raters' model rows, ascending (none for an unknown item)
+  void raters(int64_t item_id, std::vector<int64_t>& out) const;
+  // strategy 0: PreferredItemsNeighborhoodCandidateItemsStrategy, 1:
+  // AllUnknownItemsCandidateItemsStrategy, for the preferred items
+  // preferred[0, m) in preference order; out: FastIDSet iteration order
+  void candidates(const int64_t* preferred, int64_t m, int strategy, bool include_known,
+                  std::vector<int64_t>& out) const;
+
+ private:
+  ItemCandidatesImpl* p;
+};
+// ---- cms_item.hip: blocks of the similarity matrix and item-based estimates ----
+// (fixed shapes, u32 counters; rows are owner rows resolved by the caller; the
+// results are copied to the host and st is synchronised.  timed: st is the
+// handle's stream and the work is a timing scope)
+// widest sketch row the staged kernel images in LDS (wider: the pair kernel) and its right tile
+int item_max_staged_width();
+int item_right_tile();
+// out[i * nr + j] = userSimilarity(left[i], right[j])
+int item_block(cms_handle* h, QueryCtx& c, hipStream_t st, bool timed, const int64_t* left, int64_t nl,
+               const int64_t* right, int64_t nr, double* out);
+// out[i] = doEstimatePreference (item-based) of candidate row cand[i], i in
+// [cand_off[u], cand_off[u + 1]), over user u's preferences pref_rows / pref_vals
+// [pref_off[u], pref_off[u + 1])
+int item_estimates(cms_handle* h, QueryCtx& c, hipStream_t st, bool timed, int64_t n, const int64_t* pref_off,
+                   const int64_t* pref_rows, const float* pref_vals, const int64_t* cand_off, const int64_t* cand,
+                   int use_capper, float lo, float hi, float* out);
 int write_similar_items(cms_handle* h, const char* path, int32_t k, int32_t as_float);
 int write_similarities(cms_handle* h, const char* path, int32_t k, int32_t format, double threshold);
 // ---- cms_cosine_sym.hip: symmetric all-pairs waves, 256 x 192 tiles ----

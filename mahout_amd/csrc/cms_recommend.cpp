@@ -15,6 +15,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <memory>
+#include <mutex>
 #include <thread>
 #include <vector>
 
@@ -121,11 +123,22 @@ struct FastIdSet {
       if (k != kNull && k != kRemoved) add(k);
   }
 
-  bool add(int64_t key) {
+  // the head of add(): grow, or rehash in place, once too few slots are open.
+  // It runs before the lookup, so add() of a key the set already holds can
+  // still rebuild the table -- all such an add can do (touch()).
+  void make_room() {
     if ((float)slots_used * lf >= (float)keys.size()) {
       if ((float)entries * lf >= (float)slots_used) rehash(next_twin_prime((int32_t)(lf * (float)keys.size())));
       else rehash(next_twin_prime((int32_t)(lf * (float)entries)));
     }
+  }
+  // addAll() of a non-empty set whose keys are all present (no REMOVED slot
+  // since they were added): the first add's make_room(), after which the
+  // condition is false until a new key arrives
+  void touch() { make_room(); }
+
+  bool add(int64_t key) {
+    make_room();
     const int32_t index = find_for_add(key);
     const int64_t old = keys[(size_t)index];
     if (old == key) return false;
@@ -279,6 +292,109 @@ void parallel_users(int64_t n, int threads, const std::function<void(int64_t)>& 
       for (int64_t u = t; u < n; u += threads) fn(u);
     });
   for (auto& th : pool) th.join();
+}
+
+// ---- GenericItemBasedRecommender's candidate strategies ----
+// (T/impl/recommender/PreferredItemsNeighborhoodCandidateItemsStrategy.java:31-46,
+// AllUnknownItemsCandidateItemsStrategy.java:28-40) over the user CSR: the
+// item side -- getItemIDs() ascending, getPreferencesForItem's raters in
+// ascending user ID -- is the CSR transposed.
+
+struct ItemCandidatesImpl {
+  int64_t n_users;
+  const int64_t* off;
+  const int64_t* items;
+  std::vector<int64_t> item_ids;    // ascending, unique
+  std::vector<int64_t> item_off;    // [items + 1]
+  std::vector<int64_t> item_users;  // raters (model rows) of each item, ascending
+  std::vector<FastIdSet> user_sets;  // getItemIDsFromUser per model row, built on first use
+  std::unique_ptr<std::once_flag[]> user_once;
+  FastIdSet all_items{2};           // strategy 1 before the removals
+  std::once_flag all_once;
+
+  int64_t item_index(int64_t id) const {
+    return std::lower_bound(item_ids.begin(), item_ids.end(), id) - item_ids.begin();
+  }
+  const FastIdSet& user_set(int64_t r) {
+    std::call_once(user_once[(size_t)r], [&] { user_sets[(size_t)r] = item_set(items + off[r], off[r + 1] - off[r]); });
+    return user_sets[(size_t)r];
+  }
+};
+
+ItemCandidates::ItemCandidates(int64_t n_users, const int64_t* pref_offsets, const int64_t* pref_items)
+    : p(new ItemCandidatesImpl) {
+  p->n_users = n_users;
+  p->off = pref_offsets;
+  p->items = pref_items;
+  const int64_t total = n_users > 0 ? pref_offsets[n_users] : 0;
+  p->item_ids.assign(pref_items, pref_items + total);
+  std::sort(p->item_ids.begin(), p->item_ids.end());
+  p->item_ids.erase(std::unique(p->item_ids.begin(), p->item_ids.end()), p->item_ids.end());
+  const size_t ni = p->item_ids.size();
+  // counting sort of the pairs by item; the rows are walked ascending, so
+  // every item's raters come out ascending
+  std::vector<int64_t> start(ni + 1, 0), idx((size_t)total);
+  for (int64_t i = 0; i < total; ++i) ++start[(size_t)(idx[(size_t)i] = p->item_index(pref_items[i])) + 1];
+  for (size_t i = 0; i < ni; ++i) start[i + 1] += start[i];
+  std::vector<int64_t> users((size_t)total), fill(start.begin(), start.end() - 1);
+  for (int64_t r = 0; r < n_users; ++r)
+    for (int64_t i = pref_offsets[r]; i < pref_offsets[r + 1]; ++i) users[(size_t)fill[(size_t)idx[(size_t)i]]++] = r;
+  // getPreferencesForItem holds a user once: a pair the CSR repeats counts once
+  p->item_off.assign(ni + 1, 0);
+  p->item_users.reserve((size_t)total);
+  for (size_t i = 0; i < ni; ++i) {
+    for (int64_t t = start[i]; t < start[i + 1]; ++t)
+      if (t == start[i] || users[(size_t)t] != users[(size_t)t - 1]) p->item_users.push_back(users[(size_t)t]);
+    p->item_off[i + 1] = (int64_t)p->item_users.size();
+  }
+  p->user_sets.resize((size_t)n_users);
+  p->user_once.reset(new std::once_flag[(size_t)std::max<int64_t>(n_users, 1)]);
+}
+
+ItemCandidates::~ItemCandidates() { delete p; }
+
+const std::vector<int64_t>& ItemCandidates::item_ids() const { return p->item_ids; }
+
+void ItemCandidates::raters(int64_t item_id, std::vector<int64_t>& out) const {
+  out.clear();
+  const int64_t i = p->item_index(item_id);
+  if (i < (int64_t)p->item_ids.size() && p->item_ids[(size_t)i] == item_id)
+    out.assign(p->item_users.begin() + p->item_off[(size_t)i], p->item_users.begin() + p->item_off[(size_t)i + 1]);
+}
+
+void ItemCandidates::candidates(const int64_t* preferred, int64_t m, int strategy, bool include_known,
+                                std::vector<int64_t>& out) const {
+  FastIdSet possible;
+  if (strategy == 1) {
+    std::call_once(p->all_once, [&] {
+      p->all_items = FastIdSet((int32_t)p->item_ids.size());  // new FastIDSet(dataModel.getNumItems())
+      for (int64_t id : p->item_ids) p->all_items.add(id);
+    });
+    possible = p->all_items;
+  } else {
+    // a rater met again adds only keys the set holds: its addAll comes down
+    // to the table rebuild an add() may start with (FastIdSet::touch)
+    std::vector<char> seen((size_t)p->n_users, 0);
+    for (int64_t k = 0; k < m; ++k) {
+      const int64_t i = p->item_index(preferred[k]);
+      if (i >= (int64_t)p->item_ids.size() || p->item_ids[(size_t)i] != preferred[k]) continue;
+      for (int64_t t = p->item_off[(size_t)i]; t < p->item_off[(size_t)i + 1]; ++t) {
+        const int64_t r = p->item_users[(size_t)t];
+        if (seen[(size_t)r]) {
+          possible.touch();
+        } else {
+          seen[(size_t)r] = 1;
+          possible.add_all(p->user_set(r));
+        }
+      }
+    }
+  }
+  if (!include_known)
+    for (int64_t k = 0; k < m; ++k) possible.remove(preferred[k]);  // removeAll(long[])
+  out.clear();
+  out.reserve((size_t)possible.entries);
+  for (int64_t k : possible.keys)
+    if (k != kNull && k != kRemoved) out.push_back(k);
 }
 
 }  // namespace cms

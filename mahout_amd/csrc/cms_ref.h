@@ -5,6 +5,7 @@
 //   java_min, normalize_weight, cosine_finish   Math.min, normalizeWeightResult
 //   sketch_get      DoubleCountMinSketch.get(key)                     (:94-103)
 //   estimate_one    GenericUserBasedRecommender.doEstimatePreference (:134-184)
+//   item_estimate_one  GenericItemBasedRecommender.doEstimatePreference (:231-259)
 // A mode enters only through its counter accessor: the owner's depth, a
 // per-item prepared key, the raw counter at (row, sketch row, key) and the
 // scaling of a point query.  Every fp64 step is one IEEE round-to-nearest
@@ -183,6 +184,46 @@ CMS_HD float estimate_one(const Acc& acc, int64_t user_row, const int64_t* nb_ro
     }
   }
   return e;
+}
+
+// GenericItemBasedRecommender.doEstimatePreference (:231-259) for one
+// candidate item: sims[i] = itemSimilarity(candidate, the user's i-th
+// preferred item), prefs[i] that preference's value, walked in preference
+// order so the fp64 sums round as in Java.  NaN similarities are skipped,
+// preference += sim * (double) pref and total += sim (one rounded operation
+// each); count <= 1 -> NaN; (float)(preference / total); then the
+// EstimatedPreferenceCapper clamp when enabled, as in estimate_one.  The
+// running state is a struct so a caller may feed the preferences in pieces
+// (the kernel's right tiles), in order.
+struct ItemEstimate {
+  double preference = 0.0, total = 0.0;
+  int count = 0;
+  CMS_HD void add(const double* sims, const float* prefs, int64_t m) {
+    for (int64_t i = 0; i < m; ++i) {
+      const double s = sims[i];
+      if (s != s) continue;
+      preference = __dadd_rn(preference, __dmul_rn(s, (double)prefs[i]));
+      total = __dadd_rn(total, s);
+      ++count;
+    }
+  }
+  CMS_HD float finish(int use_capper, float lo, float hi) const {
+    float e = __builtin_nanf("");
+    if (count > 1) {
+      e = (float)__ddiv_rn(preference, total);
+      if (use_capper) {
+        if (e > hi) e = hi;
+        else if (e < lo) e = lo;
+      }
+    }
+    return e;
+  }
+};
+
+CMS_HD float item_estimate_one(const double* sims, const float* prefs, int64_t m, int use_capper, float lo, float hi) {
+  ItemEstimate e;
+  e.add(sims, prefs, m);
+  return e.finish(use_capper, lo, hi);
 }
 
 }  // namespace cms

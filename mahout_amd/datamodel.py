@@ -48,6 +48,20 @@ class GenericDataModel:
         self.item_ids = np.unique(self.keys)
         return self
 
+    def transposed(self):
+        """The model with users and items swapped: its "users" are this
+        model's items (ascending), each with the users that hold it as keys,
+        ascending, and the same values -- the orientation an ItemSimilarity's
+        CosineCM is built over (FileDataModel's transpose, :414-418).  A user
+        without preferences has no place in it, so transposing twice drops
+        such users."""
+        users = np.repeat(self.user_ids, np.diff(self.offsets))
+        order = np.lexsort((users, self.keys))  # by item, then by user
+        items, counts = np.unique(self.keys, return_counts=True)
+        off = np.zeros(items.size + 1, np.int64)
+        np.cumsum(counts, out=off[1:])
+        return GenericDataModel.from_csr(items, off, users[order], None if self.values is None else self.values[order])
+
     def getUserIDs(self):
         return self.user_ids
 

@@ -484,6 +484,72 @@ class SketchTable:
                                             _ptr(items), _ptr(vals)))
         return counts, items, vals
 
+    # -- item-based recommender: owners are items --
+    def similarity_block(self, ids1, ids2):
+        """cms_similarity_block: the [n1][n2] float64 block of the similarity
+        matrix, row i equal to similarities(ids1[i], ids2) bit for bit; one
+        read of each ids1 row serves all of ids2.  IDs may repeat."""
+        a = np.ascontiguousarray(ids1, np.int64).reshape(-1)
+        b = np.ascontiguousarray(ids2, np.int64).reshape(-1)
+        out = np.zeros((a.size, b.size), np.float64)
+        check(self._lib.cms_similarity_block(self._h, _ptr(a), a.size, _ptr(b), b.size, _ptr(out)))
+        return out
+
+    @staticmethod
+    def _csr(name, offsets, n, *arrays):
+        o = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        # the library reads every array up to its last offset: they must match
+        if o.size != n + 1 or o[0] != 0 or bool(np.any(np.diff(o) < 0)) or any(a.size != o[-1] for a in arrays):
+            raise ValueError(f"{name} must hold {n + 1} non-decreasing entries from 0 to the length of its arrays")
+        return o
+
+    def item_estimates_batch(self, pref_offsets, pref_items, pref_vals, cand_offsets, cand_items, capper=None):
+        """cms_item_estimates_batch: GenericItemBasedRecommender's
+        doEstimatePreference for many users over a table whose owners are
+        items.  User u's preferences are pref_items / pref_vals
+        [pref_offsets[u]:pref_offsets[u+1]] in PreferenceArray order, its
+        candidates cand_items[cand_offsets[u]:cand_offsets[u+1]]; returns one
+        float32 estimate per candidate.  capper = (min, max) or None."""
+        pi = np.ascontiguousarray(pref_items, np.int64).reshape(-1)
+        pv = np.ascontiguousarray(pref_vals, np.float32).reshape(-1)
+        ci = np.ascontiguousarray(cand_items, np.int64).reshape(-1)
+        n = np.asarray(pref_offsets).size - 1
+        po = self._csr("pref_offsets", pref_offsets, n, pi, pv)
+        co = self._csr("cand_offsets", cand_offsets, n, ci)
+        out = np.zeros(ci.size, np.float32)
+        lo, hi = capper if capper is not None else (0.0, 0.0)
+        check(self._lib.cms_item_estimates_batch(self._h, n, _ptr(po), _ptr(pi), _ptr(pv), _ptr(co), _ptr(ci),
+                                                 int(capper is not None), float(lo), float(hi), _ptr(out)))
+        return out
+
+    ITEM_STRATEGIES = {"preferred": 0, "all_unknown": 1}
+
+    def item_recommend_batch(self, user_ids, model_user_ids, pref_offsets, pref_items, pref_vals, how_many,
+                             strategy="preferred", include_known=False, capper=None):
+        """cms_item_recommend_batch: GenericItemBasedRecommender.recommend for
+        every user of user_ids over a table whose owners are the model's
+        items.  The DataModel is model_user_ids (ascending) with row r's
+        preferences pref_items / pref_vals [pref_offsets[r]:pref_offsets[r+1]].
+        strategy: "preferred" (PreferredItemsNeighborhoodCandidateItemsStrategy)
+        or "all_unknown".  Returns (counts [n], items [n][how_many], values
+        [n][how_many] float32)."""
+        us = np.ascontiguousarray(user_ids, np.int64).reshape(-1)
+        mu = np.ascontiguousarray(model_user_ids, np.int64).reshape(-1)
+        pi = np.ascontiguousarray(pref_items, np.int64).reshape(-1)
+        pv = np.ascontiguousarray(pref_vals, np.float32).reshape(-1)
+        po = self._csr("pref_offsets", pref_offsets, mu.size, pi, pv)
+        if how_many < 1:
+            raise ValueError("howMany must be at least 1")
+        counts = np.zeros(us.size, np.int32)
+        items = np.full((us.size, how_many), -1, np.int64)
+        vals = np.full((us.size, how_many), np.nan, np.float32)
+        lo, hi = capper if capper is not None else (0.0, 0.0)
+        check(self._lib.cms_item_recommend_batch(self._h, us.size, _ptr(us), mu.size, _ptr(mu), _ptr(po), _ptr(pi),
+                                                 _ptr(pv), int(self.ITEM_STRATEGIES.get(strategy, strategy)),
+                                                 int(how_many), int(bool(include_known)), int(capper is not None),
+                                                 float(lo), float(hi), _ptr(counts), _ptr(items), _ptr(vals)))
+        return counts, items, vals
+
     def write_similar_items(self, path, k, as_float=True):
         """cms_top_k_all in FileSimilarItemsWriter's CSV format."""
         check(self._lib.cms_write_similar_items(self._h, os.fsencode(path), int(k), int(as_float)))

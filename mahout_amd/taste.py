@@ -220,11 +220,17 @@ class CosineCM:
     TEMP_USER_ID is answered from the temporary preferences.
     """
 
-    def __init__(self, dataModel, conf, hfBuilder, weighting=Weighting.UNWEIGHTED, device=-1, sketches=None):
+    def __init__(self, dataModel, conf, hfBuilder, weighting=Weighting.UNWEIGHTED, device=-1, sketches=None,
+                 counters=None):
         """sketches: a checkpoint file written by saveSketches(); the sketches
         are loaded from it instead of being built from the DataModel (fixed
         shapes only; the file's shape, owners and counter type must be the
-        ones this DataModel and conf would build)."""
+        ones this DataModel and conf would build).  counters="f64" asks for
+        DoubleCountMinSketch's own fp64 counters even where the preferences
+        would fit exact u32 units (counter_units decides otherwise)."""
+        if counters not in (None, "f64"):
+            raise ValueError('counters must be None (chosen from the preferences) or "f64"')
+        self._counters = counters
         if not dataModel.hasPreferenceValues():  # CosineCM.java:38
             raise ValueError("DataModel doesn't have preference values")
         self._per_owner = isinstance(conf, CountMinSketchConfig)
@@ -250,7 +256,7 @@ class CosineCM:
 
     def _build(self):
         m = self._model
-        fb, counters = counter_units(m.offsets, m.values)
+        fb, counters = (0, "f64") if self._counters == "f64" else counter_units(m.offsets, m.values)
         try:
             if self._per_owner:
                 self._table = SketchTable(m.getNumUsers(), seed=self._hfb.seed, weighted=self._weighted,
@@ -609,6 +615,321 @@ class GenericUserBasedRecommender:
         items = self.getAllOtherItems(nb, userID, includeKnownItems).toList()
         est = self.doEstimatePreferences(userID, nb, items) if items else np.zeros(0, np.float32)
         return get_top_items(howMany, items, est)
+
+
+# ---- the item-based recommender ------------------------------------------------
+
+def build_capper(dataModel):
+    """GenericItemBasedRecommender.buildCapper (:271-278): no capper when the
+    model's min and max preference are both NaN, else (min, max) as floats."""
+    lo, hi = np.float32(dataModel.getMinPreference()), np.float32(dataModel.getMaxPreference())
+    return None if (np.isnan(lo) and np.isnan(hi)) else (float(lo), float(hi))
+
+
+def item_estimate(sims, prefs, capper=None):
+    """GenericItemBasedRecommender.doEstimatePreference (:231-259) restated:
+    sims[i] = itemSimilarity(candidate, the user's i-th item), prefs[i] that
+    item's float value.  NaN similarities are skipped; preference += sim *
+    pref and total += sim in order (fp64); fewer than two points give NaN;
+    (float)(preference / total), then the capper.  np.float32."""
+    preference = np.float64(0.0)
+    total = np.float64(0.0)
+    count = 0
+    for s, p in zip(np.asarray(sims, np.float64).tolist(), np.asarray(prefs, np.float32).tolist()):
+        if s != s:
+            continue
+        preference = preference + np.float64(s) * np.float64(p)
+        total = total + np.float64(s)
+        count += 1
+    if count <= 1:
+        return np.float32(np.nan)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        e = np.float32(preference / total)
+    if capper is not None:  # EstimatedPreferenceCapper.capEstimate
+        lo, hi = np.float32(capper[0]), np.float32(capper[1])
+        if e > hi:
+            e = hi
+        elif e < lo:
+            e = lo
+    return e
+
+
+class FullRunningAverage:
+    """T/impl/common/FullRunningAverage.java:30-55: NaN until the first datum,
+    then average * (count - 1) / count + datum / count."""
+
+    def __init__(self):
+        self.count = 0
+        self.average = float("nan")
+
+    def addDatum(self, datum):
+        self.count += 1
+        if self.count == 1:
+            self.average = float(datum)
+        else:
+            c = float(self.count)
+            self.average = self.average * float(self.count - 1) / c + float(datum) / c
+
+    def getAverage(self):
+        return self.average
+
+    def getCount(self):
+        return self.count
+
+
+def multi_most_similar_estimate(similarities, excludeItemIfNotSimilarToAll=True):
+    """MultiMostSimilarEstimator.estimate (:334-354) with no rescorer:
+    similarities = itemSimilarities(candidate, toItemIDs).  NaN enters the
+    average when excludeItemIfNotSimilarToAll (and makes it NaN); an average
+    of 0 becomes NaN."""
+    avg = FullRunningAverage()
+    for s in np.asarray(similarities, np.float64).tolist():
+        if excludeItemIfNotSimilarToAll or s == s:
+            avg.addDatum(s)
+    a = avg.getAverage()
+    return float("nan") if a == 0 else a
+
+
+class _CandidateItemsStrategy:
+    """AbstractCandidateItemsStrategy (T/impl/recommender/AbstractCandidateItemsStrategy.java):
+    both strategy interfaces over doGetCandidateItems."""
+
+    native = None  # cms_item_recommend_batch's strategy number
+
+    def __init__(self):
+        self._side = None  # (the model's arrays, its transposed model)
+
+    def _item_side(self, dataModel):
+        """getPreferencesForItem's view of a GenericDataModel: its transpose, kept per model."""
+        key = (dataModel.offsets, dataModel.keys)
+        if self._side is None or self._side[0][0] is not key[0] or self._side[0][1] is not key[1]:
+            self._side = (key, dataModel.transposed())
+        return self._side[1]
+
+    def getCandidateItems(self, *args):
+        """(userID, preferencesFromUser, dataModel, includeKnownItems) for
+        recommend, (itemIDs, dataModel) for mostSimilarItems."""
+        if len(args) == 2:
+            return self.doGetCandidateItems(args[0], args[1], False)
+        _, prefs, dataModel, includeKnownItems = args
+        return self.doGetCandidateItems(prefs[0], dataModel, includeKnownItems)
+
+    def refresh(self, alreadyRefreshed=None):
+        pass
+
+
+class PreferredItemsNeighborhoodCandidateItemsStrategy(_CandidateItemsStrategy):
+    """Every item of every user who holds one of the preferred items
+    (T/impl/recommender/PreferredItemsNeighborhoodCandidateItemsStrategy.java:31-46)."""
+
+    native = 0
+
+    def doGetCandidateItems(self, preferredItemIDs, dataModel, includeKnownItems=False):
+        side = self._item_side(dataModel)
+        possible = FastIDSet()
+        for item in np.asarray(preferredItemIDs, np.int64).tolist():
+            try:
+                raters, _ = side.getPreferencesFromUser(item)  # getPreferencesForItem: ascending user ID
+            except NoSuchUserException:
+                raise NoSuchItemException(item)
+            for u in raters.tolist():
+                keys, _ = dataModel.getPreferencesFromUser(u)
+                s = FastIDSet(len(keys))  # getItemIDsFromUser
+                for k in keys.tolist():
+                    s.add(k)
+                possible.addAll(s)
+        if not includeKnownItems:
+            for item in np.asarray(preferredItemIDs, np.int64).tolist():  # removeAll(long[])
+                possible.remove(item)
+        return possible
+
+
+class AllUnknownItemsCandidateItemsStrategy(_CandidateItemsStrategy):
+    """Every item of the model but the preferred ones
+    (T/impl/recommender/AllUnknownItemsCandidateItemsStrategy.java:28-40)."""
+
+    native = 1
+
+    def doGetCandidateItems(self, preferredItemIDs, dataModel, includeKnownItems=False):
+        possible = FastIDSet(dataModel.getNumItems())
+        for item in np.asarray(dataModel.getItemIDs(), np.int64).tolist():
+            possible.add(item)
+        if not includeKnownItems:
+            for item in np.asarray(preferredItemIDs, np.int64).tolist():
+                possible.remove(item)
+        return possible
+
+
+class GenericItemBasedRecommender:
+    """GenericItemBasedRecommender(dataModel, similarity[, candidateItemsStrategy,
+    mostSimilarItemsCandidateItemsStrategy]) (T/impl/recommender/
+    GenericItemBasedRecommender.java).  dataModel is the user-oriented model,
+    similarity an ItemSimilarity -- a CosineCM over dataModel.transposed() puts
+    every estimate of a recommend() into one device batch
+    (SketchTable.item_recommend_batch / item_estimates_batch /
+    similarity_block).  Any other ItemSimilarity, and a CosineCM whose table
+    those calls refuse (per-owner shapes, fp64 counters), is served through
+    itemSimilarities per candidate and item_estimate on the host."""
+
+    def __init__(self, dataModel, similarity, candidateItemsStrategy=None, mostSimilarItemsCandidateItemsStrategy=None):
+        if similarity is None:
+            raise ValueError("similarity is null")
+        self._model = dataModel
+        self._sim = similarity
+        self._strategy = candidateItemsStrategy or PreferredItemsNeighborhoodCandidateItemsStrategy()
+        self._ms_strategy = mostSimilarItemsCandidateItemsStrategy or PreferredItemsNeighborhoodCandidateItemsStrategy()
+        self._capper = build_capper(dataModel)
+        self._csr = None
+
+    def getSimilarity(self):
+        return self._sim
+
+    def _table(self):
+        """The similarity's sketch table when the device calls serve it, else None."""
+        s = self._sim
+        if isinstance(s, CosineCM) and not s._per_owner and s.table.counters == "u32":
+            return s.table
+        return None
+
+    def _model_csr(self):
+        """(user IDs ascending, offsets, item IDs, float values) in getPreferencesFromUser order, built once."""
+        if self._csr is None:
+            m = self._model
+            if all(hasattr(m, a) for a in ("user_ids", "offsets", "keys", "values")) and m.values is not None:
+                self._csr = (m.user_ids, m.offsets, m.keys, m.values)
+            else:
+                uids = np.asarray(m.getUserIDs(), np.int64)
+                parts = [m.getPreferencesFromUser(int(u)) for u in uids]
+                off = np.zeros(uids.size + 1, np.int64)
+                np.cumsum([len(p[0]) for p in parts], out=off[1:])
+                keys = np.concatenate([np.asarray(p[0], np.int64) for p in parts]) if parts else np.zeros(0, np.int64)
+                vals = (np.concatenate([np.ones(len(p[0]), np.float32) if p[1] is None else np.asarray(p[1], np.float32)
+                                        for p in parts]) if parts else np.zeros(0, np.float32))
+                self._csr = (uids, off, keys, vals)
+        return self._csr
+
+    def _prefs(self, userID):
+        keys, vals = self._model.getPreferencesFromUser(userID)
+        vals = np.ones(len(keys), np.float32) if vals is None else np.asarray(vals, np.float32)
+        return np.asarray(keys, np.int64), vals
+
+    # ---- estimates ----
+    def doEstimatePreferences(self, userID, itemIDs):
+        """doEstimatePreference(userID, preferencesFromUser, item) for every item (float32)."""
+        keys, vals = self._prefs(userID)
+        items = np.ascontiguousarray(itemIDs, np.int64).reshape(-1)
+        t = self._table()
+        if t is not None:
+            try:
+                return t.item_estimates_batch([0, keys.size], keys, vals, [0, items.size], items, self._capper)
+            except _lib.CmsError as e:
+                raise _map_error(e, "item")
+        return np.array([item_estimate(self._sim.itemSimilarities(int(i), keys), vals, self._capper)
+                         for i in items.tolist()], np.float32).reshape(-1)
+
+    def estimatePreference(self, userID, itemID):
+        """The user's own value when the user has the item (:142-149), else the estimate."""
+        keys, vals = self._prefs(userID)
+        hit = np.nonzero(keys == itemID)[0]
+        if hit.size:
+            return np.float32(vals[hit[0]])
+        return self.doEstimatePreferences(userID, [itemID])[0]
+
+    # ---- recommend ----
+    def getAllOtherItems(self, userID, includeKnownItems=False):
+        """AbstractRecommender.getAllOtherItems: the candidate strategy's FastIDSet."""
+        return self._strategy.getCandidateItems(userID, self._prefs(userID), self._model, includeKnownItems)
+
+    def _native_strategy(self):
+        s = self._strategy
+        return s.native if isinstance(s, _CandidateItemsStrategy) and self._table() is not None else None
+
+    def recommend(self, userID, howMany, includeKnownItems=False):
+        """recommend(userID, howMany, null, includeKnownItems) (:120-139): [(itemID, float32 value)]."""
+        return self.recommend_all([userID], howMany, includeKnownItems)[0]
+
+    def recommend_all(self, userIDs, howMany, includeKnownItems=False):
+        """recommend() for every user of userIDs: with a device-served CosineCM
+        and one of the two built-in strategies, one native call
+        (cms_item_recommend_batch); otherwise user by user on the host around
+        doEstimatePreferences.  One [(itemID, float32 value)] list per user."""
+        if howMany < 1:
+            raise ValueError("howMany must be at least 1")
+        users = np.ascontiguousarray(userIDs, np.int64).reshape(-1)
+        native = self._native_strategy()
+        if native is not None:
+            mu, po, pi, pv = self._model_csr()
+            rows = np.minimum(np.searchsorted(mu, users), max(mu.size - 1, 0))
+            bad = mu[rows] != users if mu.size else np.ones(users.size, bool)
+            if bad.any():
+                raise NoSuchUserException(int(users[bad][0]))
+            try:
+                cnt, items, vals = self._sim.table.item_recommend_batch(users, mu, po, pi, pv, howMany, native,
+                                                                        includeKnownItems, self._capper)
+            except _lib.CmsError as e:
+                raise _map_error(e, "item")
+            return [[(int(items[u, j]), vals[u, j]) for j in range(int(cnt[u]))] for u in range(users.size)]
+        out = []
+        for u in users.tolist():
+            keys, _ = self._prefs(u)
+            if keys.size == 0:
+                out.append([])
+                continue
+            items = self.getAllOtherItems(u, includeKnownItems).toList()
+            est = self.doEstimatePreferences(u, items) if items else np.zeros(0, np.float32)
+            out.append(get_top_items(howMany, items, est))
+        return out
+
+    # ---- most similar items ----
+    def _block(self, ids1, ids2):
+        """itemSimilarity(ids1[i], ids2[j]) as [n1][n2]: one device block, or itemSimilarities per row."""
+        t = self._table()
+        if t is not None:
+            try:
+                return t.similarity_block(ids1, ids2)
+            except _lib.CmsError as e:
+                raise _map_error(e, "item")
+        return np.array([self._sim.itemSimilarities(int(a), ids2) for a in ids1], np.float64).reshape(len(ids1), len(ids2))
+
+    def mostSimilarItems(self, itemIDs, howMany, excludeItemIfNotSimilarToAll=True):
+        """mostSimilarItems(itemID | itemIDs, howMany[, excludeItemIfNotSimilarToAll])
+        (:162-204): one item ranks the candidates by itemSimilarity(itemID, .);
+        several by MultiMostSimilarEstimator, the FullRunningAverage of
+        itemSimilarities(candidate, itemIDs).  [(itemID, float32 value)]."""
+        if howMany < 1:
+            raise ValueError("howMany must be at least 1")
+        single = np.ndim(itemIDs) == 0
+        to = np.ascontiguousarray([itemIDs] if single else itemIDs, np.int64).reshape(-1)
+        cands = self._ms_strategy.getCandidateItems(to, self._model).toList()
+        if not cands:
+            return []
+        if single:
+            est = self._block(to, cands)[0]
+        else:
+            est = [multi_most_similar_estimate(row, excludeItemIfNotSimilarToAll) for row in self._block(cands, to)]
+        return get_top_items(howMany, cands, est)
+
+    def recommendedBecause(self, userID, itemID, howMany):
+        """recommendedBecause (:206-222): the user's other items ranked by
+        (1.0 + itemSimilarity(itemID, item)) * preference."""
+        if howMany < 1:
+            raise ValueError("howMany must be at least 1")
+        keys, vals = self._prefs(userID)
+        own = FastIDSet(keys.size)
+        for k in keys.tolist():
+            own.add(k)
+        own.remove(itemID)
+        items = own.toList()
+        if not items:
+            return []
+        sims = self._block([itemID], items)[0]
+        pref = {int(k): float(v) for k, v in zip(keys.tolist(), vals.tolist())}
+        est = [(1.0 + float(s)) * pref[i] for i, s in zip(items, sims)]
+        return get_top_items(howMany, items, est)
+
+    def refresh(self, alreadyRefreshed=None):
+        self._capper = build_capper(self._model)
+        self._csr = None
 
 
 def _is_prime(n):
