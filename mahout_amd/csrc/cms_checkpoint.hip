@@ -1746,154 +1746,18 @@ int merge_device(cms_handle* h, const void* d_buf, int64_t bytes, Apply op) {
   return apply_resident(h, op, im, static_cast<const uint8_t*>(d_buf) + im.hd.payload_off);
 }
 
-// ---- compact ----
-
-// Every owner row re-stored in the form ckpt::compact_form gives its counters
-// as they are now (cms_compact.hip).  The scan, the rule, the re-formed
-// payload beside the table and the loader's verify pass over it all leave the
-// live rows alone: whatever can be refused is refused here, with the table as
-// it was.  Then the arena is emptied and the payload restored as a load
-// restores an image (restore_layout: no holes), and the handle's state --
-// finalized or not, its norms, its kept refresh lists -- is put back: none of
-// it depends on how a row is stored.
-// a step before the first change failed: its status (CMS_E_OOM for an
-// allocation, as hip_fail reports it) under the call's own name
-int compact_refused(int rc, int code = 0) {
-  char was[384];
-  std::snprintf(was, sizeof(was), "%s", cms_last_error());
-  return set_error(code ? code : rc, "cms_compact_table: %s; the table is unchanged", was);
-}
-
-int compact_table(cms_handle* h, int64_t* rows_changed) {
-  const int64_t n = h->n;
-  const int depth = h->p.depth;
-  Image old;  // the rows as they are: forms, place classes, bounds and masses (synchronises)
-  int rc = plan_save(h, old);
-  if (rc) return compact_refused(rc);
-  const int L = lists_allowed(h) ? h->tune.list_keys : 0;
-  const uint64_t list_mass_max =
-      L > 0 && h->p.frac_bits == 0 ? (uint64_t)std::min(std::min(L, kListMaxKeys), kListMaxEntries / depth) : 0;
-  DevBuf d_scan, d_tform, d_dst, d_sum, payload;
-  auto oom = [&](hipError_t e, const char* what) -> int {
-    if (e == hipSuccess) return CMS_OK;
-    (void)hipGetLastError();
-    return set_error(CMS_E_OOM, "cms_compact_table: no device memory for %s; the table is unchanged", what);
-  };
-  if ((rc = oom(d_scan.ensure(sizeof(uint2) * (size_t)n), "the row scan"))) return rc;
-  if ((rc = compact_scan(h, list_mass_max, d_scan.as<uint2>()))) return compact_refused(rc);
-  std::vector<uint2> scan((size_t)n);
-  auto readback = [&](void* dst, const void* src, size_t bytes) -> int {
-    CMS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-    CMS_HIP(hipStreamSynchronize(h->stream));
-    return CMS_OK;
-  };
-  if ((rc = readback(scan.data(), d_scan.ptr, sizeof(uint2) * (size_t)n))) return compact_refused(rc);
-
-  Image im;
-  im.hd = old.hd;
-  im.ids = old.ids;
-  im.dir.resize((size_t)n);
-  std::vector<uint8_t> tform((size_t)n);
-  std::vector<uint64_t> dst((size_t)n), sums((size_t)depth);
-  uint64_t at = 0;
-  int64_t changed = 0;
-  for (int64_t r = 0; r < n; ++r) {
-    const DirEntry& was = old.dir[r];
-    const uint64_t* row_sums = nullptr;
-    if (scan[r].y) {  // every sketch row sums to the mass
-      std::fill(sums.begin(), sums.end(), was.mass);
-      row_sums = sums.data();
-    }
-    uint64_t len = 0;
-    const int form = compact_form(scan[r].x, was.mass, row_sums, depth, h->p.width, h->p.frac_bits, L, h->forms_ok, &len);
-    DirEntry& e = im.dir[r];
-    e.form = (uint8_t)form;
-    e.cls = form >= kRowU1 && form <= kRowU16 ? (uint8_t)(form - kRowU1 + kCapU1) : 0;  // the form's own class
-    e.rsv = 0;
-    e.cbound = form == kRowHot ? 0u : scan[r].x;
-    e.len = len;
-    e.mass = was.mass;
-    e.off = at;
-    at += round16(len);
-    tform[r] = e.form;
-    dst[r] = e.off;
-    // as the handle will hold the row: without the compact layout every narrow
-    // row keeps a whole u16 slot, a row of zeros included
-    uint8_t held_form = e.form, held_cls = e.cls;
-    if (!h->compact && form != kRowHot) {
-      held_cls = kCapU16;
-      if (form == kRowZero) held_form = kRowU16;
-    }
-    changed += held_form != was.form || held_cls != was.cls;
-  }
-  im.hd.payload_bytes = at;
-  im.hd.file_bytes = im.hd.payload_off + at;
-  if (const char* why = check_directory(im.hd, im.dir.data(), n))
-    return set_error(CMS_E_STATE, "cms_compact_table: the re-formed directory is inconsistent (%s); the table is unchanged", why);
-
-  if ((rc = oom(payload.ensure((size_t)std::max<uint64_t>(at, 16)), "the re-formed rows"))) return rc;
-  if ((rc = oom(d_tform.ensure((size_t)n), "the row plan"))) return rc;
-  if ((rc = oom(d_dst.ensure(sizeof(uint64_t) * (size_t)n), "the row plan"))) return rc;
-  if ((rc = oom(d_sum.ensure(2 * sizeof(unsigned long long)), "the row plan"))) return rc;
-  auto plan_up = [&]() -> int {
-    CMS_HIP(hipMemcpyAsync(d_tform.ptr, tform.data(), (size_t)n, hipMemcpyHostToDevice, h->stream));
-    CMS_HIP(hipMemcpyAsync(d_dst.ptr, dst.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    CMS_HIP(hipMemsetAsync(d_sum.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
-    return CMS_OK;
-  };
-  if ((rc = plan_up())) return compact_refused(rc);
-  if ((rc = compact_pack(h, d_tform.as<uint8_t>(), d_dst.as<uint64_t>(), payload.as<uint8_t>(), at,
-                         d_sum.as<unsigned long long>())))
-    return compact_refused(rc);
-  unsigned long long sum = 0;
-  if ((rc = readback(&sum, d_sum.ptr, sizeof(sum)))) return compact_refused(rc);
-  im.hd.checksum = sum;
-  Segs sg;
-  DevBuf d_out;
-  // the loader's own pass over what the pack produced: checksum, pad bytes, every list entry.  A failure of the
-  // pass itself keeps its status; a payload that fails it is this call's own fault, not the caller's argument
-  if ((rc = verify_resident(h, im, payload.as<uint8_t>(), sg, d_out)))
-    return compact_refused(rc, rc == CMS_E_PARAM ? CMS_E_STATE : 0);
-
-  // ---- everything that can be refused has been: the old rows are given up ----
-  const bool was_finalized = h->finalized, had_norms = h->norms_valid;
-  unsigned long long res[2] = {0, 0};
-  Expand ex;  // (stays empty: compact_form gives a handle only forms it holds)
-  auto device_part = [&]() -> int {
-    int r = restore_layout(h, im, ex);
-    if (r) return r;
-    build_segs(im, sg);
-    if ((r = sg.upload(h))) return r;
-    CMS_HIP(hipMemsetAsync(d_out.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
-    if ((r = unpack_range(h, sg, 0, at / 16, payload.as<uint8_t>(), d_out.as<unsigned long long>()))) return r;
-    CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
-    CMS_HIP(hipStreamSynchronize(h->stream));
-    return CMS_OK;
-  };
-  rc = device_part();
-  if (rc || res[1] || res[0] != im.hd.checksum || !ex.rows.empty()) {
-    (void)hipGetLastError();
-    (void)leave_empty(h);
-    return set_error(CMS_E_HIP, "cms_compact_table: the table was lost while its rows were laid out anew; the handle is empty, as after cms_reset");
-  }
-  h->finalized = was_finalized;
-  h->norms_valid = had_norms;
-  h->mfma_ready = false;  // the operand images are rebuilt when next asked for
-  h->i8blk_ready = false;
-  *rows_changed = changed;
-  return CMS_OK;
-}
-
-// ---- fold: the table at a width that divides its own, as an image (cms_fold_table) ----
+// ---- the table re-encoded at a width that divides its own, as an image ----
 //
-// Compaction's route without the restore: scan the rows as they fold, give
-// every folded row compact_form's form at shape (depth, wf) and its place in
-// the payload on the host, pack.  The live table is only read.  At wf == width
-// nothing folds and the scan and the pack are the compaction's own.
+// Scan the rows as they fold (cms_fold.hip), give every folded row
+// compact_form's form at shape (depth, wf) and its place in the payload on the
+// host, pack.  The live table is only read.  cms_fold_table writes the image
+// out; cms_compact_table, at wf == width where nothing folds, restores it in
+// the table's place.
 struct FoldPlan {
   Image im;  // header, IDs and directory of the folded image (its checksum after the pack)
   std::vector<uint8_t> tform;
   std::vector<uint64_t> dst;
+  std::vector<DirEntry> was;  // the source rows' directory
 };
 
 int check_fold_width(cms_handle* h, int32_t wf) {
@@ -1906,9 +1770,11 @@ int check_fold_width(cms_handle* h, int32_t wf) {
 int fold_plan(cms_handle* h, int32_t wf, FoldPlan& fp) {
   const int64_t n = h->n;
   const int depth = h->p.depth;
-  Image old;  // the source's header, IDs and masses (synchronises)
+  Image old;  // the rows as they are: header, IDs, forms, place classes, bounds and masses (synchronises)
   int rc = plan_save(h, old);
   if (rc) return rc;
+  // the tunables alone: compact_form rechecks the shape itself (wf % 32, 2 d wf <= 80 KiB, list_keys > 0), so at
+  // wf == width they give the forms that forms_ok and lists_allowed() let the handle hold
   const bool forms = h->tune.forms;
   const int L = forms ? h->tune.list_keys : 0;
   const uint64_t list_mass_max =
@@ -1917,9 +1783,7 @@ int fold_plan(cms_handle* h, int32_t wf, FoldPlan& fp) {
   if (!h->empty) {  // (an empty handle's rows are all zero: its arrays are stale)
     DevBuf d_scan;
     CMS_HIP(d_scan.ensure(sizeof(uint2) * (size_t)n));
-    rc = wf == h->p.width ? compact_scan(h, list_mass_max, d_scan.as<uint2>())
-                          : fold_scan(h, wf, list_mass_max, d_scan.as<uint2>());
-    if (rc) return rc;
+    if ((rc = fold_scan(h, wf, list_mass_max, d_scan.as<uint2>()))) return rc;
     CMS_HIP(hipMemcpyAsync(scan.data(), d_scan.ptr, sizeof(uint2) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     CMS_HIP(hipStreamSynchronize(h->stream));
   }
@@ -1961,7 +1825,8 @@ int fold_plan(cms_handle* h, int32_t wf, FoldPlan& fp) {
   im.hd.file_bytes = im.hd.payload_off + at;
   im.hd.checksum = 0;
   if (const char* why = check_directory(im.hd, im.dir.data(), n))
-    return set_error(CMS_E_STATE, "cms_fold_table: the folded directory is inconsistent (%s)", why);
+    return set_error(CMS_E_STATE, "the directory of the rows re-formed at width %d is inconsistent (%s)", (int)wf, why);
+  fp.was = std::move(old.dir);
   return CMS_OK;
 }
 
@@ -1977,16 +1842,96 @@ int fold_payload(cms_handle* h, int32_t wf, FoldPlan& fp, uint8_t* d_payload) {
   CMS_HIP(hipMemcpyAsync(d_tform.ptr, fp.tform.data(), (size_t)n, hipMemcpyHostToDevice, h->stream));
   CMS_HIP(hipMemcpyAsync(d_dst.ptr, fp.dst.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
   CMS_HIP(hipMemsetAsync(d_sum.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
-  const int rc = wf == h->p.width
-                     ? compact_pack(h, d_tform.as<uint8_t>(), d_dst.as<uint64_t>(), d_payload, at, d_sum.as<unsigned long long>())
-                     : fold_pack(h, wf, d_tform.as<uint8_t>(), d_dst.as<uint64_t>(), d_payload, at, d_sum.as<unsigned long long>());
-  if (rc) return rc;
+  if (int rc = fold_pack(h, wf, d_tform.as<uint8_t>(), d_dst.as<uint64_t>(), d_payload, at, d_sum.as<unsigned long long>()))
+    return rc;
   unsigned long long sum = 0;
   CMS_HIP(hipMemcpyAsync(&sum, d_sum.ptr, sizeof(sum), hipMemcpyDeviceToHost, h->stream));
   CMS_HIP(hipStreamSynchronize(h->stream));
   fp.im.hd.checksum = sum;
   return CMS_OK;
 }
+
+// ---- compact ----
+
+// Every owner row re-stored in the form ckpt::compact_form gives its counters
+// as they are now: the plan and the payload above at the table's own width.
+// The scan, the rule, the re-formed payload beside the table and the loader's
+// verify pass over it all leave the live rows alone: whatever can be refused
+// is refused here, with the table as it was.  Then the arena is emptied and
+// the payload restored as a load restores an image (restore_layout: no
+// holes), and the handle's state -- finalized or not, its norms, its kept
+// refresh lists -- is put back: none of it depends on how a row is stored.
+
+// a step before the first change failed: its status (CMS_E_OOM for an
+// allocation, as hip_fail reports it) under the call's own name
+int compact_refused(int rc, int code = 0) {
+  char was[384];
+  std::snprintf(was, sizeof(was), "%s", cms_last_error());
+  (void)hipGetLastError();  // (a refused allocation is not the next launch's error)
+  return set_error(code ? code : rc, "cms_compact_table: %s; the table is unchanged", was);
+}
+
+int compact_table(cms_handle* h, int64_t* rows_changed) {
+  const int64_t n = h->n;
+  FoldPlan fp;
+  int rc = fold_plan(h, h->p.width, fp);
+  if (rc) return compact_refused(rc);
+  Image& im = fp.im;
+  int64_t changed = 0;
+  for (int64_t r = 0; r < n; ++r) {
+    // as the handle will hold the row: without the compact layout every narrow
+    // row keeps a whole u16 slot, a row of zeros included
+    uint8_t held_form = im.dir[r].form, held_cls = im.dir[r].cls;
+    if (!h->compact && held_form != kRowHot) {
+      held_cls = kCapU16;
+      if (held_form == kRowZero) held_form = kRowU16;
+    }
+    changed += held_form != fp.was[r].form || held_cls != fp.was[r].cls;
+  }
+  const uint64_t at = im.hd.payload_bytes;
+  DevBuf payload;
+  if (payload.ensure((size_t)std::max<uint64_t>(at, 16)) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_error(CMS_E_OOM, "cms_compact_table: no device memory for the re-formed rows; the table is unchanged");
+  }
+  if ((rc = fold_payload(h, h->p.width, fp, payload.as<uint8_t>()))) return compact_refused(rc);
+  Segs sg;
+  DevBuf d_out;
+  // the loader's own pass over what the pack produced: checksum, pad bytes, every list entry.  A failure of the
+  // pass itself keeps its status; a payload that fails it is this call's own fault, not the caller's argument
+  if ((rc = verify_resident(h, im, payload.as<uint8_t>(), sg, d_out)))
+    return compact_refused(rc, rc == CMS_E_PARAM ? CMS_E_STATE : 0);
+
+  // ---- everything that can be refused has been: the old rows are given up ----
+  const bool was_finalized = h->finalized, had_norms = h->norms_valid;
+  unsigned long long res[2] = {0, 0};
+  Expand ex;  // (stays empty: compact_form gives a handle only forms it holds)
+  auto device_part = [&]() -> int {
+    int r = restore_layout(h, im, ex);
+    if (r) return r;
+    build_segs(im, sg);
+    if ((r = sg.upload(h))) return r;
+    CMS_HIP(hipMemsetAsync(d_out.ptr, 0, 2 * sizeof(unsigned long long), h->stream));
+    if ((r = unpack_range(h, sg, 0, at / 16, payload.as<uint8_t>(), d_out.as<unsigned long long>()))) return r;
+    CMS_HIP(hipMemcpyAsync(res, d_out.ptr, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+    CMS_HIP(hipStreamSynchronize(h->stream));
+    return CMS_OK;
+  };
+  rc = device_part();
+  if (rc || res[1] || res[0] != im.hd.checksum || !ex.rows.empty()) {
+    (void)hipGetLastError();
+    (void)leave_empty(h);
+    return set_error(CMS_E_HIP, "cms_compact_table: the table was lost while its rows were laid out anew; the handle is empty, as after cms_reset");
+  }
+  h->finalized = was_finalized;
+  h->norms_valid = had_norms;
+  h->mfma_ready = false;  // the operand images are rebuilt when next asked for
+  h->i8blk_ready = false;
+  *rows_changed = changed;
+  return CMS_OK;
+}
+
+// ---- fold: the image written out (cms_fold_table) ----
 
 int fold_device(cms_handle* h, int32_t wf, void* d_buf, int64_t capacity, int64_t* bytes) {
   FoldPlan fp;

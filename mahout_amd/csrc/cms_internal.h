@@ -546,20 +546,12 @@ int retract_validate(cms_handle* h, const int64_t* d_rows, const float* d_val, i
 // decrements exceed it, and then nothing was written.  Blocking.
 int retract_coo_device(cms_handle* h, const int64_t* d_row, const int64_t* d_key, const float* d_val, int64_t n,
                        bool by_id);
-// ---- cms_compact.hip (cms_compact_table; the driver is in cms_checkpoint.hip) ----
-// d_scan[r] = (largest counter of owner row r, 1 when every sketch row sums to
-// the row mass -- asked only of rows whose mass is in [1, list_mass_max])
-int compact_scan(cms_handle* h, uint64_t list_mass_max, uint2* d_scan);
-// every row re-encoded in the form d_tform[r] (ckpt::kRow*) at d_payload +
-// d_dst[r]; the payload is zeroed first and *d_sum += its checksum
-int compact_pack(cms_handle* h, const uint8_t* d_tform, const uint64_t* d_dst, uint8_t* d_payload, uint64_t payload_bytes,
-                 unsigned long long* d_sum);
-// ---- cms_fold.hip (cms_fold_table; the driver is in cms_checkpoint.hip) ----
-// wf divides the handle's width and is at most half of it (wf == width is the
-// compaction's scan and pack).  d_scan[r] = (largest counter of owner row r
-// folded to width wf, saturated at 2^32 - 1; bit 0: every sketch row sums to
-// the row mass, asked as compact_scan asks it; bit 1: a folded counter reached
-// 2^32)
+// ---- cms_fold.hip (cms_fold_table, and cms_compact_table at wf == width; the driver is in cms_checkpoint.hip) ----
+// wf divides the handle's width; the timing scopes are compact_scan /
+// compact_pack at wf == width, fold_scan / fold_pack below it.  d_scan[r] =
+// (largest counter of owner row r folded to width wf, saturated at 2^32 - 1;
+// bit 0: every sketch row sums to the row mass -- asked only of rows whose mass
+// is in [1, list_mass_max]; bit 1: a folded counter reached 2^32)
 int fold_scan(cms_handle* h, int32_t wf, uint64_t list_mass_max, uint2* d_scan);
 // every row folded to width wf and encoded in the form d_tform[r] (ckpt::kRow*)
 // at d_payload + d_dst[r]; the payload is zeroed first and *d_sum += its checksum

@@ -1,7 +1,7 @@
 // cms_rows.h -- device helpers shared by the kernels that re-encode whole owner
-// rows, one workgroup of 256 lanes per row: cms_compact.hip (a row in its
-// narrowest form) and cms_fold.hip (a row folded to a narrower width).  Where
-// a row's counters are now, 16 of them at a time out of any dense form and into
+// rows, one workgroup of 256 lanes per row (cms_fold.hip: a row folded to a
+// divisor width, or at its own width in its narrowest form).  Where a row's
+// counters are now, 16 of them at a time out of any dense form and into
 // any dense form, the payload checksum of what is stored, and the workgroup's
 // reduce and scan.
 #pragma once

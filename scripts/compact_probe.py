@@ -8,7 +8,8 @@ taken in the same process on the same pre-compaction table:
                         are the fresh table's, the forms are not; then compact()
 
   compact_scan / compact_pack   the library's timing scopes (kernel time) of
-                        the two new kernels; ckpt_verify / ckpt_unpack the
+                        k_fold_scan / k_fold_pack at the table's own width;
+                        ckpt_verify / ckpt_unpack the
                         restore's
   yardstick             save_device() (ckpt_pack) + reset() + load_device()
                         (ckpt_unpack) of the pre-compaction table: the same rows

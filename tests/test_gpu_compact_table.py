@@ -1,8 +1,8 @@
-"""GPU: a live sketch table compacted (cms_compact_table: k_compact_scan, the
-host's ckpt::compact_form, k_compact_pack, then the loader's verify pass and
-restore_layout / k_ckpt_unpack).  Every comparison is bit for bit against the
-no-GPU specification checkpoint.compact_checkpoint of the table's own image
-before the call, and the counters against what they were.
+"""GPU: a live sketch table compacted (cms_compact_table: k_fold_scan at the
+table's own width, the host's ckpt::compact_form, k_fold_pack, then the
+loader's verify pass and restore_layout / k_ckpt_unpack).  Every comparison is
+bit for bit against the no-GPU specification checkpoint.compact_checkpoint of
+the table's own image before the call, and the counters against what they were.
 
 Tables are installed with load_device(build_checkpoint(...)), every row in a
 form and place class wider than its counters need.  The shapes are the
@@ -228,6 +228,8 @@ def test_every_source_form_into_every_target_form(oracle, n, d, w):
         stored0 = t.stats()["stored_bytes"]
         tab0 = t.read_counters()
         assert np.array_equal(tab0, counters)
+        # the fold at the table's own width is the compaction as an image (whatever layout the handle holds)
+        assert bytes(t.fold_device(w).cpu().numpy().tobytes()) == spec
         changed = t.compact()
         after = _image(t)
         _assert_image(after, spec, w)
