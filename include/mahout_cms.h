@@ -123,7 +123,9 @@ int cms_shape_from_delta_epsilon(double delta, double epsilon, int32_t* width, i
  *   CMS_NO_FP4=1          no e2m1 operand image: every single-limb pair on int8 MFMA
  *   CMS_NO_MLS=1          multi-limb slabs on the 128-row tile kernel instead of k_cosine_mls
  *   CMS_THRESHOLD_SLAB_ROWS=<rows>  query rows per slab of cms_threshold_neighbors, rounded up to
- *                         whole 128-row tiles (default: the top-k's slab budget) */
+ *                         whole 128-row tiles (default: the top-k's slab budget)
+ *   CMS_EXACT_TILE=<rows> candidate rows per workgroup of the exact cosine's tile kernel, rounded up
+ *                         to a multiple of 64 (default and most: 8192, 64 KiB of LDS cells) */
 int cms_create(const cms_params* p, cms_handle** out);
 void cms_destroy(cms_handle* h);
 const char* cms_last_error(void);
@@ -789,6 +791,46 @@ int cms_fold_table_device(cms_handle* h, int32_t new_width, void* d_buf, int64_t
  * not a checkpoint, has an unknown version, or is shorter or longer than its
  * header claims.  file_bytes may be NULL. */
 int cms_checkpoint_info(const char* path, cms_params* out, int64_t* file_bytes);
+
+/* ---- the exact CosineSimilarity ------------------------------------------------
+ * CosineSimilarity.userSimilarity (T/impl/similarity/CosineSimilarity.java:44-103)
+ * over the owners' raw preferences: the quantity the sketch cosine
+ * approximates.  sumX2, sumXY and sumY2 are the reference's sequential fp64
+ * sums (sumXY over the common items, in id1's preference order); NaN when
+ * either list is empty or Math.sqrt(sumX2) * Math.sqrt(sumY2) == 0.0; else
+ * sumXY / denominator and normalizeWeightResult(result, count, count) with
+ * count = the two list lengths' sum (AbstractSimilarity.java:313-330) under the
+ * handle's weighting.  Every result equals the reference's bit for bit.
+ *
+ * The DataModel of the handle's num_owners rows as a host CSR (row i <->
+ * cms_set_owner_ids' ids[i]): offsets [n + 1] from 0, never decreasing; a
+ * row's keys strictly ascending, as GenericDataModel gives them; vals the
+ * preference values (any float).  CMS_E_PARAM otherwise, and then the handle
+ * keeps what it had.  Works on every handle kind, before or after
+ * cms_finalize, and neither reads nor writes the sketch table; a second call
+ * replaces the model.  Timing scope "exact_attach". */
+int cms_exact_attach_csr(cms_handle* h, const int64_t* offsets, const int64_t* keys, const float* vals);
+/* Frees the model (cms_destroy does too).  The calls below return
+ * CMS_E_STATE while no model is attached. */
+int cms_exact_detach(cms_handle* h);
+/* out[t] = userSimilarity(id1, ids2[t]); owner IDs as cms_similarities takes
+ * them (CMS_E_NO_SUCH_ID).  Timing scope "exact_pairs". */
+int cms_exact_similarities(cms_handle* h, int64_t id1, const int64_t* ids2, int64_t m, double* out);
+/* out[t] = userSimilarity(ids1[t], ids2[t]). */
+int cms_exact_pairs(cms_handle* h, const int64_t* ids1, const int64_t* ids2, int64_t m, double* out);
+/* The k most similar owners of each owner ROW rows[q] (any order, repeats
+ * allowed), laid out and ordered as cms_top_k_rows: TopItems.getTopUsers, NaN
+ * skipped, the row itself excluded, similarity descending then owner ID
+ * ascending; ids / scores [nq][k] (padding: ID -1, NaN), counts [nq]; scores
+ * may be NULL.  k in [1, 512].  Timing scopes "exact_tile", "exact_pairs",
+ * "top_k". */
+int cms_exact_top_k_rows(cms_handle* h, const int64_t* rows, int64_t nq, int32_t k, int64_t* ids, double* scores,
+                         int32_t* counts);
+/* rows[i] = the owner row of ids[i] (cms_set_owner_ids, or the IDs a loaded
+ * checkpoint installed); CMS_E_NO_SUCH_ID for an unknown ID.  Host only. */
+int cms_owner_rows(cms_handle* h, const int64_t* ids, int64_t m, int64_t* rows);
+/* The same list for one owner ID, as cms_most_similar returns it. */
+int cms_exact_most_similar(cms_handle* h, int64_t id, int32_t k, int64_t* out_ids, double* out_scores, int32_t* count);
 
 /* ---- instrumentation ------------------------------------------------------- */
 typedef struct cms_stats {

@@ -56,6 +56,8 @@ EXPORTS = [
     "cms_fold_size", "cms_fold_table", "cms_fold_table_device",
     "cms_threshold_neighbors", "cms_fastidset_to_array",
     "cms_similarity_block", "cms_item_estimates_batch", "cms_item_recommend_batch",
+    "cms_exact_attach_csr", "cms_exact_detach", "cms_exact_similarities", "cms_exact_pairs", "cms_exact_top_k_rows",
+    "cms_exact_most_similar", "cms_owner_rows",
 ]
 
 
@@ -203,6 +205,13 @@ _SIGS = {
     "cms_item_estimates_batch": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_float, ctypes.c_float, _vp]),
     "cms_item_recommend_batch": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
                                         ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
+    "cms_exact_attach_csr": (_int, [_vp, _vp, _vp, _vp]),
+    "cms_exact_detach": (_int, [_vp]),
+    "cms_exact_similarities": (_int, [_vp, _i64, _vp, _i64, _vp]),
+    "cms_exact_pairs": (_int, [_vp, _vp, _vp, _i64, _vp]),
+    "cms_exact_top_k_rows": (_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "cms_exact_most_similar": (_int, [_vp, _i64, _i32, _vp, _vp, ctypes.POINTER(_i32)]),
+    "cms_owner_rows": (_int, [_vp, _vp, _i64, _vp]),
 }
 
 _lib = None

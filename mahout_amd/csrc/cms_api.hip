@@ -358,6 +358,7 @@ static int create_impl(const cms_params* p, bool per_owner, cms_handle** out) {
     h->tune.mls = !flag("CMS_NO_MLS");
     if (const int rows = num("CMS_THRESHOLD_SLAB_ROWS", 0); rows > 0)  // whole 128-row tiles, at least one
       h->tune.threshold_slab_rows = std::max<int64_t>(128, ((int64_t)rows + 127) / 128 * 128);
+    h->tune.exact_tile = std::max(0, num("CMS_EXACT_TILE", 0));
   }
   h->per_owner = per_owner;
   h->f64 = f64;
@@ -469,6 +470,7 @@ void cms_destroy(cms_handle* h) {
   if (h->ev_fork2) (void)hipEventDestroy(h->ev_fork2);
   if (h->ev_join2) (void)hipEventDestroy(h->ev_join2);
   free_query_pool(h);
+  exact_release(h);
   if (h->comm) (void)ncclCommDestroy(h->comm);
   arena_release(h);
   void* bufs[] = {h->d_off, h->d_t64, h->d_hidx, h->d_cbound, h->d_row_mass, h->d_norm, h->d_norm_sqrt, h->d_rowmax, h->d_flags, h->d_owner_ids};
@@ -1672,6 +1674,107 @@ int cms_anonymous_most_similar(cms_handle* h, int64_t nq, const int64_t* offsets
 int cms_anonymous_batch(cms_handle* h, int32_t elem_bytes, int32_t* batch) {
   if (!h || !batch || (elem_bytes != 2 && elem_bytes != 4)) return set_error(CMS_E_PARAM, "bad argument");
   *batch = anon_batch_size(h->p.width, elem_bytes);
+  return CMS_OK;
+}
+
+// ---- the exact CosineSimilarity over an attached DataModel (cms_exact.hip) ----
+
+static int exact_require(cms_handle* h, const char* what) {
+  if (!h->exact) return set_error(CMS_E_STATE, "%s: no DataModel is attached (cms_exact_attach_csr)", what);
+  return CMS_OK;
+}
+
+int cms_exact_attach_csr(cms_handle* h, const int64_t* offsets, const int64_t* keys, const float* vals) {
+  if (!h || !offsets) return set_error(CMS_E_PARAM, "null argument");
+  Guard g(h);
+  if (offsets[0] == 0 && offsets[h->n] > 0 && (!keys || !vals))
+    return set_error(CMS_E_PARAM, "cms_exact_attach_csr: the DataModel needs keys and preference values");
+  return exact_attach(h, offsets, keys, vals);
+}
+
+int cms_exact_detach(cms_handle* h) {
+  if (!h) return set_error(CMS_E_PARAM, "null handle");
+  Guard g(h);
+  (void)hipStreamSynchronize(h->stream);
+  exact_release(h);
+  return CMS_OK;
+}
+
+int cms_exact_similarities(cms_handle* h, int64_t id1, const int64_t* ids2, int64_t m, double* out) {
+  if (!h || m < 0 || (m > 0 && (!ids2 || !out))) return set_error(CMS_E_PARAM, "null argument");
+  Guard g(h);
+  int rc = exact_require(h, "cms_exact_similarities");
+  if (rc) return rc;
+  int64_t q;
+  if ((rc = row_of(h, id1, &q))) return rc;
+  std::vector<int64_t> rows((size_t)m);
+  for (int64_t i = 0; i < m; ++i)
+    if ((rc = row_of(h, ids2[i], &rows[(size_t)i]))) return rc;
+  return exact_pair_call(h, &q, 1, rows.data(), m, true, out);
+}
+
+int cms_exact_pairs(cms_handle* h, const int64_t* ids1, const int64_t* ids2, int64_t m, double* out) {
+  if (!h || m < 0 || (m > 0 && (!ids1 || !ids2 || !out))) return set_error(CMS_E_PARAM, "null argument");
+  Guard g(h);
+  int rc = exact_require(h, "cms_exact_pairs");
+  if (rc) return rc;
+  std::vector<int64_t> r1((size_t)m), r2((size_t)m);
+  for (int64_t i = 0; i < m; ++i)
+    if ((rc = row_of(h, ids1[i], &r1[(size_t)i])) || (rc = row_of(h, ids2[i], &r2[(size_t)i]))) return rc;
+  return exact_pair_call(h, r1.data(), m, r2.data(), m, false, out);
+}
+
+int cms_owner_rows(cms_handle* h, const int64_t* ids, int64_t m, int64_t* rows) {
+  if (!h || m < 0 || (m > 0 && (!ids || !rows))) return set_error(CMS_E_PARAM, "null argument");
+  SharedGuard g(h);
+  for (int64_t i = 0; i < m; ++i)
+    if (int rc = row_of(h, ids[i], &rows[i])) return rc;
+  return CMS_OK;
+}
+
+// the top-k of owner rows under the handle's lock, copied to the host
+static int exact_top_k_host(cms_handle* h, const int64_t* rows, int64_t nq, int32_t k, int64_t* ids, double* scores,
+                            int32_t* counts);
+
+int cms_exact_most_similar(cms_handle* h, int64_t id, int32_t k, int64_t* out_ids, double* out_scores, int32_t* count) {
+  if (!h || !out_ids || !count) return set_error(CMS_E_PARAM, "null argument");
+  if (k < 1 || k > kCandCap / 2) return set_error(CMS_E_PARAM, "k must be in [1, %d]", kCandCap / 2);
+  Guard g(h);
+  int rc = exact_require(h, "cms_exact_most_similar");
+  if (rc) return rc;
+  int64_t row;
+  if ((rc = row_of(h, id, &row))) return rc;
+  return exact_top_k_host(h, &row, 1, k, out_ids, out_scores, count);
+}
+
+int cms_exact_top_k_rows(cms_handle* h, const int64_t* rows, int64_t nq, int32_t k, int64_t* ids, double* scores,
+                         int32_t* counts) {
+  if (!h || nq < 0 || (nq > 0 && (!rows || !ids || !counts))) return set_error(CMS_E_PARAM, "null argument");
+  if (k < 1 || k > kCandCap / 2) return set_error(CMS_E_PARAM, "k must be in [1, %d]", kCandCap / 2);
+  Guard g(h);
+  int rc = exact_require(h, "cms_exact_top_k_rows");
+  if (rc) return rc;
+  return exact_top_k_host(h, rows, nq, k, ids, scores, counts);
+}
+
+static int exact_top_k_host(cms_handle* h, const int64_t* rows, int64_t nq, int32_t k, int64_t* ids, double* scores,
+                            int32_t* counts) {
+  int rc;
+  for (int64_t i = 0; i < nq; ++i)
+    if (rows[i] < 0 || rows[i] >= h->n) return set_error(CMS_E_PARAM, "owner row outside [0, num_owners)");
+  if (nq == 0) return CMS_OK;
+  DevBuf o_ids, o_sc, o_cnt;
+  const size_t cells = (size_t)nq * (size_t)k;
+  CMS_HIP(o_ids.ensure(sizeof(int64_t) * cells));
+  CMS_HIP(o_sc.ensure(sizeof(double) * cells));
+  CMS_HIP(o_cnt.ensure(sizeof(int32_t) * (size_t)nq));
+  CMS_HIP(hipMemsetAsync(o_ids.ptr, 0xFF, sizeof(int64_t) * cells, h->stream));  // padding: ID -1, all-ones NaN
+  CMS_HIP(hipMemsetAsync(o_sc.ptr, 0xFF, sizeof(double) * cells, h->stream));
+  if ((rc = exact_top_k_rows(h, rows, nq, k, o_ids.as<int64_t>(), o_sc.as<double>(), o_cnt.as<int32_t>()))) return rc;
+  CMS_HIP(hipMemcpyAsync(ids, o_ids.ptr, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, h->stream));
+  if (scores) CMS_HIP(hipMemcpyAsync(scores, o_sc.ptr, sizeof(double) * cells, hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipMemcpyAsync(counts, o_cnt.ptr, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
   return CMS_OK;
 }
 

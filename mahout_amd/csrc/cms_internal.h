@@ -229,7 +229,9 @@ struct Tunables {
   bool fp4 = true;         // CMS_NO_FP4=1: no e2m1 operand image (every single-limb pair on int8)
   bool mls = true;         // CMS_NO_MLS=1: multi-limb slabs on the 128-tile kernel instead of k_cosine_mls
   int64_t threshold_slab_rows = 0;  // CMS_THRESHOLD_SLAB_ROWS: query rows per chunk of threshold_rows (0: slab_rows_for)
+  int exact_tile = 0;       // CMS_EXACT_TILE: candidate rows per workgroup of k_exact_tile, a multiple of 64 (0: kExactTile)
 };
+struct ExactModel;  // the attached DataModel of the exact cosine (cms_exact.hip)
 }  // namespace cms
 
 struct cms_handle {
@@ -368,6 +370,8 @@ struct cms_handle {
   // bucket lists [Q][d][w], the per-(profile, row) norms / square roots / list
   // lengths and per-profile maxima, the explicit owner rows, the outputs
   cms::DevBuf an_in, an_sk, an_nz, an_meta, an_rows, an_out;
+  // the owners' DataModel for CosineSimilarity (cms_exact_attach_csr); null: none attached
+  cms::ExactModel* exact = nullptr;
   // pair-by-pair retraction (cms_retract.hip): per-owner batch masses, pair
   // counts and offsets, the run lists and the batch's grouped order
   cms::DevBuf ws_retract;
@@ -709,6 +713,20 @@ int anon_build(cms_handle* h, AnonBatch& ab, int64_t c0, int64_t qc);
 // userSimilarity(profile c0 + q, owner row d_rows[t] (null: row t)) for q < qc,
 // t < ncols into d_out[q * ld + t]
 int anon_cosines(cms_handle* h, const AnonBatch& ab, const int64_t* d_rows, int64_t ncols, double* d_out, int64_t ld);
+// ---- cms_exact.hip: CosineSimilarity over the attached DataModel ----
+// (h->exact is non-null for every call but exact_attach and exact_release)
+// a validated-here host CSR of the handle's n owner rows becomes the model; a
+// refusal (CMS_E_PARAM) leaves the handle as it was
+int exact_attach(cms_handle* h, const int64_t* off, const int64_t* keys, const float* vals);
+void exact_release(cms_handle* h);
+// host rows in, host results out (blocking).  cross: out[i * n2 + j] =
+// userSimilarity(r1[i], r2[j]); else n2 == n1 and out[t] = userSimilarity(r1[t], r2[t])
+int exact_pair_call(cms_handle* h, const int64_t* r1, int64_t n1, const int64_t* r2, int64_t n2, bool cross,
+                    double* out);
+// the k most similar owners of the owner rows rows[0, nq) (host) into device
+// outputs laid out as top_k_rows' (entries past a count are not written)
+int exact_top_k_rows(cms_handle* h, const int64_t* rows, int64_t nq, int32_t k, int64_t* d_ids, double* d_scores,
+                     int32_t* d_counts);
 // ---- cms_f64.hip (CMS_COUNTER_F64) ----
 int f64_ingest_csr(cms_handle* h, const int64_t* d_off, const int64_t* d_key, const float* d_val);
 int f64_ingest_coo_host(cms_handle* h, const int64_t* owner, const int64_t* key, const float* val, int64_t np);

@@ -131,7 +131,6 @@ class SketchTable:
     def set_owner_ids(self, ids):
         ids = np.ascontiguousarray(ids, np.int64)
         check(self._lib.cms_set_owner_ids(self._h, _ptr(ids), ids.size))
-
     def hash_params(self):
         """(a_i, b_i) of every hash row: depth rows, or all CMS_MAX_DEPTH (32)
         rows of a per-owner handle (any owner's shape may use them)."""
@@ -355,6 +354,72 @@ class SketchTable:
         check(self._lib.cms_estimate_preferences(self._h, int(user_id), _ptr(nb), nb.size, _ptr(it), it.size,
                                                  int(capper is not None), float(lo), float(hi), _ptr(out)))
         return out
+
+    # -- the exact CosineSimilarity over an attached DataModel --
+    def attach_exact(self, offsets, keys=None, vals=None):
+        """The owners' DataModel for the exact cosine (cms_exact_attach_csr):
+        a CSR over the table's owner rows (keys strictly ascending within a
+        row), or a GenericDataModel whose users are the owners.  The sketch
+        table is neither read nor written; a second call replaces the model."""
+        if keys is None and hasattr(offsets, "offsets"):
+            model = offsets
+            if not model.hasPreferenceValues():
+                raise ValueError("DataModel doesn't have preference values")
+            offsets, keys, vals = model.offsets, model.keys, model.values
+        offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        keys = np.ascontiguousarray(keys, np.int64).reshape(-1)
+        vals = np.ascontiguousarray(vals, np.float32).reshape(-1)
+        if offsets.size != self.num_owners + 1:
+            raise ValueError("offsets needs num_owners + 1 entries")
+        if keys.size != vals.size or (offsets.size and int(offsets.max()) > keys.size):
+            raise ValueError("offsets reach past the keys, or keys and vals differ in length")
+        check(self._lib.cms_exact_attach_csr(self._h, _ptr(offsets), _ptr(keys), _ptr(vals)))
+
+    def owner_rows(self, owner_ids):
+        """The owner rows of owner IDs (cms_owner_rows; CMS_E_NO_SUCH_ID for an unknown one)."""
+        ids = np.ascontiguousarray(owner_ids, np.int64).reshape(-1)
+        rows = np.zeros(ids.size, np.int64)
+        check(self._lib.cms_owner_rows(self._h, _ptr(ids), ids.size, _ptr(rows)))
+        return rows
+
+    def detach_exact(self):
+        check(self._lib.cms_exact_detach(self._h))
+
+    def exact_similarities(self, id1, ids2):
+        """CosineSimilarity.userSimilarity(id1, ids2[t]) over the attached model."""
+        ids2 = np.ascontiguousarray(ids2, np.int64).reshape(-1)
+        out = np.zeros(ids2.size, np.float64)
+        check(self._lib.cms_exact_similarities(self._h, int(id1), _ptr(ids2), ids2.size, _ptr(out)))
+        return out
+
+    def exact_pairs(self, ids1, ids2):
+        """CosineSimilarity.userSimilarity(ids1[t], ids2[t]), element-wise."""
+        ids1 = np.ascontiguousarray(ids1, np.int64).reshape(-1)
+        ids2 = np.ascontiguousarray(ids2, np.int64).reshape(-1)
+        if ids1.size != ids2.size:
+            raise ValueError("ids1 and ids2 differ in length")
+        out = np.zeros(ids1.size, np.float64)
+        check(self._lib.cms_exact_pairs(self._h, _ptr(ids1), _ptr(ids2), ids1.size, _ptr(out)))
+        return out
+
+    def exact_top_k_rows(self, rows, k):
+        """The k most similar owners of each owner row under the exact cosine:
+        ids [nq][k], scores [nq][k] (padding: ID -1, NaN) and counts [nq],
+        ordered as top_k_rows orders them."""
+        rows = np.ascontiguousarray(rows, np.int64).reshape(-1)
+        ids = np.zeros((rows.size, k), np.int64)
+        sc = np.zeros((rows.size, k), np.float64)
+        cnt = np.zeros(rows.size, np.int32)
+        check(self._lib.cms_exact_top_k_rows(self._h, _ptr(rows), rows.size, int(k), _ptr(ids), _ptr(sc), _ptr(cnt)))
+        return ids, sc, cnt
+
+    def exact_most_similar(self, owner_id, k):
+        """mostSimilarUserIDs(owner_id, k) under the exact cosine: (ids, scores)."""
+        ids = np.zeros(k, np.int64)
+        sc = np.zeros(k, np.float64)
+        cnt = ctypes.c_int32()
+        check(self._lib.cms_exact_most_similar(self._h, int(owner_id), int(k), _ptr(ids), _ptr(sc), ctypes.byref(cnt)))
+        return ids[:cnt.value], sc[:cnt.value]
 
     # -- anonymous profiles: preferences that are no row of the table --
     @staticmethod

@@ -432,6 +432,87 @@ class CosineCM:
         self._table.close()
 
 
+class CosineSimilarity:
+    """CosineSimilarity(DataModel[, Weighting]) (T/impl/similarity/CosineSimilarity.java:32-103):
+    the full-norm cosine over the raw preferences, the quantity CosineCM's
+    sketch cosine approximates, computed on the GPU (cms_exact_*) with the
+    reference's values bit for bit.
+
+    Owners are the DataModel's users.  Over a transposed DataModel the owners
+    are items and itemSimilarity / itemSimilarities / allSimilarItemIDs are
+    this cosine between their rating vectors, in the sense in which CosineCM
+    offers them.  The object owns a minimal handle whose sketch table is never
+    ingested; only the attached model is used."""
+
+    def __init__(self, dataModel, weighting=Weighting.UNWEIGHTED, device=-1):
+        if not dataModel.hasPreferenceValues():  # CosineSimilarity.java:41
+            raise ValueError("DataModel doesn't have preference values")
+        self._model = dataModel
+        self._table = SketchTable(dataModel.getNumUsers(), depth=1, width=32, weighted=weighting == Weighting.WEIGHTED,
+                                  device=device, owner_ids=dataModel.getUserIDs())
+        try:
+            self._table.attach_exact(dataModel)
+        except _lib.CmsError as e:
+            self._table.close()
+            raise _map_error(e)
+
+    @property
+    def table(self):
+        return self._table
+
+    def userSimilarity(self, userID1, userID2):
+        try:
+            return float(self._table.exact_similarities(userID1, [userID2])[0])
+        except _lib.CmsError as e:
+            raise _map_error(e, "user")
+
+    def userSimilarities(self, userID1, userID2s):
+        try:
+            return self._table.exact_similarities(userID1, userID2s)
+        except _lib.CmsError as e:
+            raise _map_error(e, "user")
+
+    def itemSimilarity(self, itemID1, itemID2):
+        try:
+            return float(self._table.exact_similarities(itemID1, [itemID2])[0])
+        except _lib.CmsError as e:
+            raise _map_error(e, "item")
+
+    def itemSimilarities(self, itemID1, itemID2s):
+        try:
+            return self._table.exact_similarities(itemID1, itemID2s)
+        except _lib.CmsError as e:
+            raise _map_error(e, "item")
+
+    def allSimilarItemIDs(self, itemID):
+        """AbstractItemSimilarity.allSimilarItemIDs: every owner whose
+        similarity is not NaN (T/impl/similarity/AbstractItemSimilarity.java:48-58)."""
+        ids = self._model.getUserIDs()
+        sims = self.itemSimilarities(itemID, ids)
+        return ids[~np.isnan(sims)]
+
+    def mostSimilarUserIDs(self, userID, howMany):
+        """GenericUserBasedRecommender.mostSimilarUserIDs (:119-127) with
+        TopItems.getTopUsers (TopItems.java:91-136)."""
+        if howMany < 1:
+            raise ValueError("howMany must be at least 1")
+        try:
+            ids, _ = self._table.exact_most_similar(userID, howMany)
+        except _lib.CmsError as e:
+            raise _map_error(e, "user")
+        return ids
+
+    def refresh(self, alreadyRefreshed=None):
+        """Refreshable.refresh: the attached model is the DataModel's again."""
+        try:
+            self._table.attach_exact(self._model)
+        except _lib.CmsError as e:
+            raise _map_error(e)
+
+    def close(self):
+        self._table.close()
+
+
 class NearestNUserNeighborhood:
     """NearestNUserNeighborhood(n, similarity, model): the n most similar
     users (T/impl/neighborhood/NearestNUserNeighborhood.java) -- TopItems
