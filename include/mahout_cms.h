@@ -831,6 +831,33 @@ int cms_exact_top_k_rows(cms_handle* h, const int64_t* rows, int64_t nq, int32_t
 int cms_owner_rows(cms_handle* h, const int64_t* ids, int64_t m, int64_t* rows);
 /* The same list for one owner ID, as cms_most_similar returns it. */
 int cms_exact_most_similar(cms_handle* h, int64_t id, int32_t k, int64_t* out_ids, double* out_scores, int32_t* count);
+/* GenericUserBasedRecommender.doEstimatePreference over a similarity that is
+ * no CosineCM (GenericUserBasedRecommender.java:134-184, sim == null) for n
+ * users, shaped as cms_estimate_preferences_batch: a neighbour's preference is
+ * the attached model's raw float for the item -- an absent item is no data
+ * point, a present 0.0 is one -- and theSimilarity is this section's
+ * userSimilarity(user, neighbour), skipped when NaN; the neighbours are taken
+ * in the caller's order, the user itself skipped; fewer than two data points
+ * give NaN, else (float)(preference / totalSimilarity) and the capper.  A key
+ * the model lacks gives NaN; keys may repeat and come in any order.  Every
+ * estimate equals the reference's bit for bit.  One user is a batch of one.
+ * Argument rules and errors as cms_estimate_preferences_batch; CMS_E_STATE
+ * without a model.  The sketch table is neither read nor written.  Timing
+ * scopes "exact_pairs", "exact_estimate". */
+int cms_exact_estimate_preferences_batch(cms_handle* h, int64_t n, const int64_t* user_ids, const int64_t* nb_offsets,
+                                         const int64_t* neighbor_ids, const int64_t* item_offsets,
+                                         const int64_t* item_keys, int32_t use_capper, float cap_min, float cap_max,
+                                         float* out);
+/* GenericUserBasedRecommender.recommend for n users over that estimate, shaped
+ * as cms_recommend_batch with the attached model as the DataModel (owner rows
+ * are its rows): getAllOtherItems in FastIDSet order on host threads, one
+ * estimate batch, TopItems.getTopItems.  out_counts[n] (0 for an empty
+ * neighbourhood), out_items / out_values [n][how_many].  An unknown user or
+ * neighbour ID is CMS_E_NO_SUCH_ID, and nothing is written. */
+int cms_exact_recommend_batch(cms_handle* h, int64_t n, const int64_t* user_ids, const int64_t* nb_offsets,
+                              const int64_t* neighbor_ids, int32_t how_many, int32_t include_known, int32_t use_capper,
+                              float cap_min, float cap_max, int32_t* out_counts, int64_t* out_items,
+                              float* out_values);
 
 /* ---- instrumentation ------------------------------------------------------- */
 typedef struct cms_stats {

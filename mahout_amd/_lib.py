@@ -58,6 +58,7 @@ EXPORTS = [
     "cms_similarity_block", "cms_item_estimates_batch", "cms_item_recommend_batch",
     "cms_exact_attach_csr", "cms_exact_detach", "cms_exact_similarities", "cms_exact_pairs", "cms_exact_top_k_rows",
     "cms_exact_most_similar", "cms_owner_rows",
+    "cms_exact_estimate_preferences_batch", "cms_exact_recommend_batch",
 ]
 
 
@@ -212,6 +213,10 @@ _SIGS = {
     "cms_exact_top_k_rows": (_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "cms_exact_most_similar": (_int, [_vp, _i64, _i32, _vp, _vp, ctypes.POINTER(_i32)]),
     "cms_owner_rows": (_int, [_vp, _vp, _i64, _vp]),
+    "cms_exact_estimate_preferences_batch": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _int, ctypes.c_float,
+                                                    ctypes.c_float, _vp]),
+    "cms_exact_recommend_batch": (_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _int, ctypes.c_float, ctypes.c_float,
+                                         _vp, _vp, _vp]),
 }
 
 _lib = None

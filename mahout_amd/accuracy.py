@@ -93,3 +93,62 @@ def sketch_accuracy(table, owner_ids, k):
         "sketch_list": _errors(s_sc[s_valid], x_at_s),
         "exact_list": _errors(s_at_e, e_sc[e_valid]),
     }
+
+
+def _estimates_at(recommender, users, lists):
+    """The recommender's own estimate (doEstimatePreferences with its own
+    neighbourhood) at every (users[u], item of lists[u]) in (user, list) order."""
+    off, nb = recommender._nb.getUserNeighborhoods(users)  # the lists getUserNeighborhood gives, in one pass
+    parts = []
+    for u, lst in enumerate(lists):
+        if lst:
+            est = recommender.doEstimatePreferences(int(users[u]), nb[off[u]:off[u + 1]], [i for i, _ in lst])
+            parts.append(np.asarray(est, np.float64))
+    return np.concatenate(parts + [np.zeros(0, np.float64)])
+
+
+def _values(lists):
+    return np.array([v for lst in lists for _, v in lst], np.float64)
+
+
+def recommendation_accuracy(sketch_recommender, exact_recommender, user_ids, how_many):
+    """What the sketch does to what a user is shown: the recommendations of a
+    taste.GenericUserBasedRecommender over a CosineCM (sketch_recommender)
+    against those of one over a taste.CosineSimilarity (exact_recommender),
+    both over the same DataModel, for the users user_ids (nu of them) at list
+    length how_many.  Every list and estimate comes from the library; only the
+    reduction is numpy.
+
+    Returns a dict.  With S_u = sketch_recommender.recommend_all(user_ids,
+    how_many)[u] and E_u = exact_recommender.recommend_all(user_ids,
+    how_many)[u], each a [(itemID, float32 value)] list:
+
+      sketch_lists, exact_lists   S and E
+      precision_at_n [nu]   |{items of S_u} & {items of E_u}| / len(E_u); 1.0 when E_u is empty
+      exact_list         over the pairs (u, item of E_u) in (user, list) order, with x = the
+                         exact list's value and s = sketch_recommender.doEstimatePreferences(u,
+                         its own neighbourhood of u, items of E_u), e = s - x over the pairs
+                         where neither is NaN:
+                           pairs            how many such pairs
+                           nan_pairs        pairs left out (s or x is NaN)
+                           abs_err_mean     np.abs(e).mean()
+                           abs_err_max      np.abs(e).max()
+                           signed_err_mean  e.mean()
+                         (the three figures are NaN when pairs == 0)
+      sketch_list        the same over the pairs (u, item of S_u), with s = the sketch list's
+                         value and x = exact_recommender.doEstimatePreferences(u, its own
+                         neighbourhood of u, items of S_u)
+    """
+    users = np.ascontiguousarray(user_ids, np.int64).reshape(-1)
+    s_lists = sketch_recommender.recommend_all(users, how_many)
+    e_lists = exact_recommender.recommend_all(users, how_many)
+    precision = np.ones(users.size, np.float64)
+    for u, (s, e) in enumerate(zip(s_lists, e_lists)):
+        if e:
+            precision[u] = len({i for i, _ in s} & {i for i, _ in e}) / len(e)
+    return {
+        "sketch_lists": s_lists, "exact_lists": e_lists,
+        "precision_at_n": precision,
+        "exact_list": _errors(_estimates_at(sketch_recommender, users, e_lists), _values(e_lists)),
+        "sketch_list": _errors(_values(s_lists), _estimates_at(exact_recommender, users, s_lists)),
+    }

@@ -359,6 +359,7 @@ static int create_impl(const cms_params* p, bool per_owner, cms_handle** out) {
     if (const int rows = num("CMS_THRESHOLD_SLAB_ROWS", 0); rows > 0)  // whole 128-row tiles, at least one
       h->tune.threshold_slab_rows = std::max<int64_t>(128, ((int64_t)rows + 127) / 128 * 128);
     h->tune.exact_tile = std::max(0, num("CMS_EXACT_TILE", 0));
+    h->tune.exact_est_tile = std::max(0, num("CMS_EXACT_EST_TILE", 0));
   }
   h->per_owner = per_owner;
   h->f64 = f64;
@@ -1230,6 +1231,38 @@ int cms_estimate_preferences_batch(cms_handle* h, int64_t n, const int64_t* user
   return CMS_OK;
 }
 
+// GenericUserBasedRecommender.recommend for n users around one estimate batch:
+// the candidates per user on host threads (model rows: nb_rows, user_rows, -1
+// for a user the model lacks), estimate(it_off, keys, est) for all of them at
+// once, then TopItems.getTopItems per user.
+extern "C++" {
+template <class Estimate>
+static int recommend_flow(int64_t n, const int64_t* nb_offsets, const int64_t* nb_rows, const int64_t* user_rows,
+                          const int64_t* pref_offsets, const int64_t* pref_items, int32_t how_many,
+                          int32_t include_known, int32_t* out_counts, int64_t* out_items, float* out_values,
+                          Estimate estimate) {
+  std::vector<std::vector<int64_t>> cand((size_t)n);
+  const int threads = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
+  parallel_users(n, threads, [&](int64_t u) {
+    if (nb_offsets[u + 1] == nb_offsets[u]) return;  // recommend(): an empty neighbourhood recommends nothing
+    recommend_candidates(nb_rows + nb_offsets[u], nb_offsets[u + 1] - nb_offsets[u], user_rows[u], pref_offsets,
+                         pref_items, include_known != 0, cand[(size_t)u]);
+  });
+  std::vector<int64_t> it_off((size_t)n + 1, 0);
+  for (int64_t u = 0; u < n; ++u) it_off[(size_t)u + 1] = it_off[(size_t)u] + (int64_t)cand[(size_t)u].size();
+  std::vector<int64_t> keys((size_t)it_off[(size_t)n]);
+  for (int64_t u = 0; u < n; ++u) std::copy(cand[(size_t)u].begin(), cand[(size_t)u].end(), keys.begin() + it_off[(size_t)u]);
+  std::vector<float> est(keys.size());
+  if (int rc = estimate(it_off.data(), keys.data(), est.data())) return rc;
+  parallel_users(n, threads, [&](int64_t u) {
+    const int64_t o = it_off[(size_t)u];
+    out_counts[u] = recommend_top_items(how_many, keys.data() + o, est.data() + o, it_off[(size_t)u + 1] - o,
+                                        out_items + u * (int64_t)how_many, out_values + u * (int64_t)how_many);
+  });
+  return CMS_OK;
+}
+}  // extern "C++"
+
 int cms_recommend_batch(cms_handle* h, int64_t n, const int64_t* user_ids, const int64_t* nb_offsets,
                         const int64_t* neighbor_ids, int64_t n_model_users, const int64_t* model_user_ids,
                         const int64_t* pref_offsets, const int64_t* pref_items, int32_t how_many,
@@ -1273,28 +1306,12 @@ int cms_recommend_batch(cms_handle* h, int64_t n, const int64_t* user_ids, const
       if ((nb_rows[(size_t)j] = model_row(neighbor_ids[j])) < 0)
         return set_error(CMS_E_NO_SUCH_ID, "no such user ID %lld in the data model", (long long)neighbor_ids[j]);
   }
-  // candidates per user (host threads), then one concatenated estimate batch
-  std::vector<std::vector<int64_t>> cand((size_t)n);
-  const int threads = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
-  parallel_users(n, threads, [&](int64_t u) {
-    if (nb_offsets[u + 1] == nb_offsets[u]) return;  // recommend(): an empty neighbourhood recommends nothing
-    recommend_candidates(nb_rows.data() + nb_offsets[u], nb_offsets[u + 1] - nb_offsets[u], user_rows[(size_t)u],
-                         pref_offsets, pref_items, include_known != 0, cand[(size_t)u]);
-  });
-  std::vector<int64_t> it_off((size_t)n + 1, 0);
-  for (int64_t u = 0; u < n; ++u) it_off[(size_t)u + 1] = it_off[(size_t)u] + (int64_t)cand[(size_t)u].size();
-  std::vector<int64_t> keys((size_t)it_off[(size_t)n]);
-  for (int64_t u = 0; u < n; ++u) std::copy(cand[(size_t)u].begin(), cand[(size_t)u].end(), keys.begin() + it_off[(size_t)u]);
-  std::vector<float> est(keys.size());
-  if (int rc = cms_estimate_preferences_batch(h, n, user_ids, nb_offsets, neighbor_ids, it_off.data(), keys.data(),
-                                              use_capper, cap_min, cap_max, est.data()))
-    return rc;
-  parallel_users(n, threads, [&](int64_t u) {
-    const int64_t o = it_off[(size_t)u];
-    out_counts[u] = recommend_top_items(how_many, keys.data() + o, est.data() + o, it_off[(size_t)u + 1] - o,
-                                        out_items + u * (int64_t)how_many, out_values + u * (int64_t)how_many);
-  });
-  return CMS_OK;
+  return recommend_flow(n, nb_offsets, nb_rows.data(), user_rows.data(), pref_offsets, pref_items, how_many,
+                        include_known, out_counts, out_items, out_values,
+                        [&](const int64_t* it_off, const int64_t* keys, float* est) {
+                          return cms_estimate_preferences_batch(h, n, user_ids, nb_offsets, neighbor_ids, it_off, keys,
+                                                                use_capper, cap_min, cap_max, est);
+                        });
 }
 
 // ---- item-based recommender (cms_item.hip): similarity blocks, batched estimates ----
@@ -1776,6 +1793,73 @@ static int exact_top_k_host(cms_handle* h, const int64_t* rows, int64_t nq, int3
   CMS_HIP(hipMemcpyAsync(counts, o_cnt.ptr, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
   CMS_HIP(hipStreamSynchronize(h->stream));
   return CMS_OK;
+}
+
+// the owner rows of a batch's users [n] and neighbours [nb_offsets[n]], under the handle's lock
+static int exact_batch_rows(cms_handle* h, int64_t n, const int64_t* user_ids, const int64_t* nb_offsets,
+                            const int64_t* neighbor_ids, std::vector<int64_t>& user_rows,
+                            std::vector<int64_t>& nb_rows) {
+  user_rows.resize((size_t)n);
+  nb_rows.resize((size_t)nb_offsets[n]);
+  for (int64_t u = 0; u < n; ++u) {
+    if (int rc = row_of(h, user_ids[u], &user_rows[(size_t)u])) return rc;
+    for (int64_t j = nb_offsets[u]; j < nb_offsets[u + 1]; ++j)
+      if (int rc = row_of(h, neighbor_ids[j], &nb_rows[(size_t)j])) return rc;
+  }
+  return CMS_OK;
+}
+
+int cms_exact_estimate_preferences_batch(cms_handle* h, int64_t n, const int64_t* user_ids, const int64_t* nb_offsets,
+                                         const int64_t* neighbor_ids, const int64_t* item_offsets,
+                                         const int64_t* item_keys, int32_t use_capper, float cap_min, float cap_max,
+                                         float* out) {
+  if (!h || n < 0 || (n > 0 && (!user_ids || !nb_offsets || !item_offsets)))
+    return set_error(CMS_E_PARAM, "null argument");
+  if (n == 0) return CMS_OK;
+  if (nb_offsets[0] != 0 || item_offsets[0] != 0) return set_error(CMS_E_PARAM, "offsets must start at 0");
+  for (int64_t u = 0; u < n; ++u)
+    if (nb_offsets[u + 1] < nb_offsets[u] || item_offsets[u + 1] < item_offsets[u])
+      return set_error(CMS_E_PARAM, "offsets must not decrease");
+  const int64_t M = nb_offsets[n], Q = item_offsets[n];
+  if ((M > 0 && !neighbor_ids) || (Q > 0 && (!item_keys || !out))) return set_error(CMS_E_PARAM, "null argument");
+  if (Q >= (int64_t(1) << 31)) return set_error(CMS_E_PARAM, "too many candidate items in one batch");
+  Guard g(h);
+  int rc = exact_require(h, "cms_exact_estimate_preferences_batch");
+  if (rc) return rc;
+  std::vector<int64_t> user_rows, nb_rows;
+  if ((rc = exact_batch_rows(h, n, user_ids, nb_offsets, neighbor_ids, user_rows, nb_rows))) return rc;
+  return exact_estimate_batch(h, n, user_rows.data(), nb_offsets, nb_rows.data(), item_offsets, item_keys, use_capper,
+                              cap_min, cap_max, out);
+}
+
+int cms_exact_recommend_batch(cms_handle* h, int64_t n, const int64_t* user_ids, const int64_t* nb_offsets,
+                              const int64_t* neighbor_ids, int32_t how_many, int32_t include_known, int32_t use_capper,
+                              float cap_min, float cap_max, int32_t* out_counts, int64_t* out_items,
+                              float* out_values) {
+  if (!h || n < 0 || (n > 0 && (!user_ids || !nb_offsets || !out_counts || !out_items || !out_values)))
+    return set_error(CMS_E_PARAM, "null argument");
+  if (how_many < 1) return set_error(CMS_E_PARAM, "howMany must be at least 1");
+  if (n == 0) return CMS_OK;
+  if (nb_offsets[0] != 0) return set_error(CMS_E_PARAM, "nb_offsets must start at 0");
+  for (int64_t u = 0; u < n; ++u)
+    if (nb_offsets[u + 1] < nb_offsets[u]) return set_error(CMS_E_PARAM, "nb_offsets must not decrease");
+  if (nb_offsets[n] > 0 && !neighbor_ids) return set_error(CMS_E_PARAM, "null argument");
+  Guard g(h);
+  int rc = exact_require(h, "cms_exact_recommend_batch");
+  if (rc) return rc;
+  // the attached model is the DataModel: owner rows are its rows
+  std::vector<int64_t> user_rows, nb_rows;
+  if ((rc = exact_batch_rows(h, n, user_ids, nb_offsets, neighbor_ids, user_rows, nb_rows))) return rc;
+  const int64_t *pref_offsets, *pref_items;
+  exact_host_csr(h, &pref_offsets, &pref_items);
+  return recommend_flow(n, nb_offsets, nb_rows.data(), user_rows.data(), pref_offsets, pref_items, how_many,
+                        include_known, out_counts, out_items, out_values,
+                        [&](const int64_t* it_off, const int64_t* keys, float* est) {
+                          if (it_off[n] >= (int64_t(1) << 31))
+                            return set_error(CMS_E_PARAM, "too many candidate items in one batch");
+                          return exact_estimate_batch(h, n, user_rows.data(), nb_offsets, nb_rows.data(), it_off, keys,
+                                                      use_capper, cap_min, cap_max, est);
+                        });
 }
 
 extern "C++" {

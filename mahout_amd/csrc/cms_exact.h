@@ -153,6 +153,19 @@ CMS_HD int exact_tile_for(int asked) {
   return t > kExactTile ? kExactTile : t;
 }
 
+// ---- the estimate kernel's shape ----
+// Candidate slots of one (user, tile) in LDS: per slot the dense item index
+// (i32), preference and totalSimilarity (f64) and count (i32), 24 bytes; 2048
+// slots are 48 KiB, so three workgroups share a CU's 160 KiB.
+// CMS_EXACT_EST_TILE overrides it with any multiple of 64 up to the default.
+constexpr int kExactEstTile = 2048;
+constexpr int kExactEstSlotBytes = 24;
+CMS_HD int exact_est_tile_for(int asked) {
+  if (asked <= 0) return kExactEstTile;
+  int t = (asked + 63) / 64 * 64;
+  return t > kExactEstTile ? kExactEstTile : t;
+}
+
 }  // namespace cms
 
 #if !defined(__HIP_DEVICE_COMPILE__)

@@ -23,7 +23,10 @@
 //     It serves the explicit-pair calls, a query row that is not
 //     integer-eligible (scored whole), and the non-eligible candidate columns
 //     of every query, re-scored after the tile pass;
-//   - the top-k is launch_top_k on the slab, as the sketch paths call it.
+//   - the top-k is launch_top_k on the slab, as the sketch paths call it;
+//   - k_exact_estimate: GenericUserBasedRecommender.doEstimatePreference over
+//     the raw preferences (the sim == null branch), one workgroup per (user,
+//     tile of T candidate slots) -- see the kernel.
 //
 // Why the tile's value is the reference's, bit for bit: for two owners with
 // U < 2^53 every partial sum the reference forms is an integer multiple of
@@ -34,27 +37,34 @@
 
 #include <algorithm>
 #include <memory>
+#include <thread>
 #include <vector>
 
 #include "cms_exact.h"
+#include "cms_exact_plan.h"
 #include "cms_internal.h"
+#include "cms_ref.h"
 
 namespace cms {
 
 constexpr int kExactThreads = 512;      // 8 waves; two workgroups per CU at the default tile
 constexpr int kExactPairThreads = 256;
+constexpr int kExactEstThreads = 256;   // three workgroups per CU at the default tile (48 KiB each)
 constexpr int64_t kExactChunkMax = 16384;  // query rows per slab chunk (the tile grid is chunk x tiles)
 
 struct ExactModel {
   int64_t n = 0, npairs = 0, nitems = 0;
   int shift = kExactNoShift;
   std::vector<uint8_t> h_seq;  // [n] 1: not integer-eligible
+  std::vector<int64_t> ids;    // [nitems] getItemIDs(): the keys, sorted and unique (key -> dense item index)
+  std::vector<int64_t> h_off, h_keys;  // the attached CSR's offsets and keys: the DataModel of the recommend call
   int64_t n_seq = 0;
   DevBuf off, item, val, unit;  // owner side: [n + 1] i64, [np] dense item (i32), float, unit (i32)
   DevBuf ioff, irow, iunit;     // item side: [nitems + 1] i64, [np] owner row ascending (i32), unit (i32)
   DevBuf U, root;               // [n] saturating sum of squared units (u64), Math.sqrt(sumX2) (f64)
   DevBuf seq_rows;              // [n_seq] the non-eligible rows (i64)
   DevBuf q1, q2, sel, out;      // a call's rows, selected queries and results
+  DevBuf e_urow, e_nboff, e_slot, e_tiles, e_est;  // an estimate batch: users' rows, neighbour offsets, plan, estimates
 };
 
 struct ExactView {
@@ -166,6 +176,102 @@ static int launch_pairs(cms_handle* h, const ExactPairArgs& g) {
   return CMS_OK;
 }
 
+// ---- the estimate kernel ----
+// GenericUserBasedRecommender.doEstimatePreference with sim == null
+// (T/impl/recommender/GenericUserBasedRecommender.java:134-184) for the
+// candidate slots of one (user, tile): the neighbourhood is walked in the
+// caller's order (:147); the user itself is skipped (:148); pref is the
+// neighbour's raw float for the item, an absent item being no data point and
+// a present 0.0 being one (:159-161); theSimilarity is sims[j], the exact
+// userSimilarity(user, neighbour) of k_exact_pairs, skipped when NaN
+// (:162-163); per data point ItemEstimate::add of that one element (:164-166)
+// and at the end ItemEstimate::finish (:172-183).
+//
+// Block b holds tile b's slots in LDS: their dense item indices, ascending,
+// and an ItemEstimate each (preference, total, count), zeroed.  The neighbours
+// are taken one after another by the whole workgroup.  The neighbour's item
+// list ascends as the slots do: a binary search finds its first item at or
+// past the tile's first slot, the threads walk the list from there to the
+// tile's last item, and each thread looks its item up among the slots (binary
+// search in LDS) and, on a hit, adds its data point to that slot.  A
+// neighbour's items are distinct, so one slot is touched by one thread per
+// neighbour: no atomics, and no sum depends on which thread ran when.  The
+// barrier between two neighbours keeps every slot's sums in neighbourhood
+// order.  The work is the neighbours' list lengths within the tile's range,
+// times the log of the tile.
+struct ExactEstArgs {
+  const int64_t* urow;      // [n] the users' owner rows
+  const int64_t* nb_off;    // [n + 1] user u's neighbours: nb_row / sims [nb_off[u], nb_off[u + 1])
+  const int64_t* nb_row;    // the neighbours' owner rows
+  const double* sims;       // userSimilarity(user, neighbour)
+  const ExactEstTile* tiles;
+  const int32_t* slot_item;  // [S]
+  float* est;                // [S]
+  int32_t T, use_capper;
+  float lo, hi;
+};
+
+__global__ __launch_bounds__(kExactEstThreads) void k_exact_estimate(ExactView v, ExactEstArgs g) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char exact_est_lds[];
+  double* preference = reinterpret_cast<double*>(exact_est_lds);
+  double* total = preference + g.T;
+  int32_t* slot = reinterpret_cast<int32_t*>(total + g.T);
+  int32_t* count = slot + g.T;
+  const ExactEstTile tile = g.tiles[blockIdx.x];
+  const int len = tile.len;  // >= 1
+  for (int i = threadIdx.x; i < len; i += kExactEstThreads) {
+    slot[i] = g.slot_item[tile.lo + i];
+    preference[i] = 0.0;
+    total[i] = 0.0;
+    count[i] = 0;
+  }
+  __syncthreads();
+  const int32_t first = slot[0], last = slot[len - 1];
+  const int64_t x = g.urow[tile.user];
+  const int64_t jhi = g.nb_off[tile.user + 1];
+  for (int64_t j = g.nb_off[tile.user]; j < jhi; ++j) {
+    const int64_t y = g.nb_row[j];
+    const double s = g.sims[j];
+    if (y == x || s != s) continue;  // the same for every thread: no slot is touched, no barrier is owed
+    int64_t a = v.off[y];
+    const int64_t hi = v.off[y + 1];
+    for (int64_t b = hi; a < b;) {  // the neighbour's first item at or past the tile's
+      const int64_t mid = (a + b) >> 1;
+      if (v.item[mid] < first) a = mid + 1;
+      else b = mid;
+    }
+    for (int64_t t = a + threadIdx.x; t < hi; t += kExactEstThreads) {
+      const int32_t it = v.item[t];
+      if (it > last) break;
+      int lo = 0;
+      for (int up = len; lo < up;) {
+        const int mid = (lo + up) >> 1;
+        if (slot[mid] < it) lo = mid + 1;
+        else up = mid;
+      }
+      if (lo < len && slot[lo] == it) {
+        ItemEstimate e;
+        e.preference = preference[lo];
+        e.total = total[lo];
+        e.count = count[lo];
+        const float pref = v.val[t];
+        e.add(&s, &pref, 1);
+        preference[lo] = e.preference;
+        total[lo] = e.total;
+        count[lo] = e.count;
+      }
+    }
+    __syncthreads();
+  }
+  for (int i = threadIdx.x; i < len; i += kExactEstThreads) {
+    ItemEstimate e;
+    e.preference = preference[i];
+    e.total = total[i];
+    e.count = count[i];
+    g.est[tile.lo + i] = e.finish(g.use_capper, g.lo, g.hi);
+  }
+}
+
 // ---- host side ----
 
 void exact_release(cms_handle* h) {
@@ -236,6 +342,9 @@ int exact_attach(cms_handle* h, const int64_t* off, const int64_t* keys, const f
     }
   }
   m->n_seq = (int64_t)seq_rows.size();
+  m->h_off.assign(off, off + n + 1);
+  m->h_keys.assign(keys, keys + np);
+  m->ids = std::move(ids);
   int rc;
   {
     TimedScope ts(h, "exact_attach");
@@ -313,6 +422,60 @@ int exact_top_k_rows(cms_handle* h, const int64_t* rows, int64_t nq, int32_t k, 
     // (launch_top_k synchronises the stream: sel and qs may go)
     if ((rc = launch_top_k(h, slab, qs, k, nullptr, d_ids, d_scores, d_counts))) return rc;
   }
+  return CMS_OK;
+}
+
+void exact_host_csr(const cms_handle* h, const int64_t** off, const int64_t** keys) {
+  *off = h->exact->h_off.data();
+  *keys = h->exact->h_keys.data();
+}
+
+int exact_estimate_batch(cms_handle* h, int64_t n, const int64_t* user_rows, const int64_t* nb_offsets,
+                         const int64_t* nb_rows, const int64_t* item_offsets, const int64_t* item_keys,
+                         int32_t use_capper, float cap_min, float cap_max, float* out) {
+  ExactModel& m = *h->exact;
+  const int64_t M = nb_offsets[n], Q = item_offsets[n];
+  if (Q == 0) return CMS_OK;
+  const int T = exact_est_tile_for(h->tune.exact_est_tile);
+  ExactEstPlan plan;
+  exact_plan_estimates(m.ids, n, item_offsets, item_keys, T, plan, [](int64_t users, auto f) {
+    parallel_users(users, (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency())), f);
+  });
+  const size_t S = plan.slot_item.size();
+  std::vector<float> est(S);
+  if (S > 0) {
+    // userSimilarity(user, neighbour) of every pair of the batch (:162): one elementwise launch
+    std::vector<int64_t> pair_user((size_t)M);
+    for (int64_t u = 0; u < n; ++u)
+      std::fill(pair_user.begin() + nb_offsets[u], pair_user.begin() + nb_offsets[u + 1], user_rows[u]);
+    const int rc = [&]() -> int {
+      int rc;
+      if ((rc = upload(h, m.q1, pair_user)) || (rc = upload(h, m.q2, nb_rows, (size_t)M)) ||
+          (rc = upload(h, m.e_urow, user_rows, (size_t)n)) || (rc = upload(h, m.e_nboff, nb_offsets, (size_t)n + 1)) ||
+          (rc = upload(h, m.e_slot, plan.slot_item)) || (rc = upload(h, m.e_tiles, plan.tiles)))
+        return rc;
+      CMS_HIP(m.out.ensure(sizeof(double) * (size_t)std::max<int64_t>(M, 1)));
+      CMS_HIP(m.e_est.ensure(sizeof(float) * S));
+      ExactPairArgs pg{m.q1.as<int64_t>(), m.q2.as<int64_t>(), nullptr, M, M, 0, 0, m.out.as<double>(), M};
+      if ((rc = launch_pairs(h, pg))) return rc;
+      ExactEstArgs g{m.e_urow.as<int64_t>(),       m.e_nboff.as<int64_t>(), m.q2.as<int64_t>(),  m.out.as<double>(),
+                     m.e_tiles.as<ExactEstTile>(), m.e_slot.as<int32_t>(),  m.e_est.as<float>(), (int32_t)T,
+                     use_capper,                   cap_min,                 cap_max};
+      {
+        TimedScope ts(h, "exact_estimate");
+        hipLaunchKernelGGL(k_exact_estimate, dim3((unsigned)plan.tiles.size()), dim3(kExactEstThreads),
+                           (size_t)kExactEstSlotBytes * (size_t)T, h->stream, exact_view(h), g);
+        CMS_HIP(hipGetLastError());
+      }
+      CMS_HIP(hipMemcpyAsync(est.data(), m.e_est.ptr, sizeof(float) * S, hipMemcpyDeviceToHost, h->stream));
+      return CMS_OK;
+    }();
+    const hipError_t synced = hipStreamSynchronize(h->stream);  // whatever was queued is done with the host arrays
+    if (rc) return rc;
+    CMS_HIP(synced);
+  }
+  // back to the caller's positions; a key the model lacks has no data point
+  for (int64_t i = 0; i < Q; ++i) out[i] = plan.pos_slot[(size_t)i] < 0 ? __builtin_nanf("") : est[(size_t)plan.pos_slot[(size_t)i]];
   return CMS_OK;
 }
 

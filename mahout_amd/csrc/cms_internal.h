@@ -230,6 +230,7 @@ struct Tunables {
   bool mls = true;         // CMS_NO_MLS=1: multi-limb slabs on the 128-tile kernel instead of k_cosine_mls
   int64_t threshold_slab_rows = 0;  // CMS_THRESHOLD_SLAB_ROWS: query rows per chunk of threshold_rows (0: slab_rows_for)
   int exact_tile = 0;       // CMS_EXACT_TILE: candidate rows per workgroup of k_exact_tile, a multiple of 64 (0: kExactTile)
+  int exact_est_tile = 0;   // CMS_EXACT_EST_TILE: candidate slots per workgroup of k_exact_estimate, a multiple of 64 (0: kExactEstTile)
 };
 struct ExactModel;  // the attached DataModel of the exact cosine (cms_exact.hip)
 }  // namespace cms
@@ -727,6 +728,18 @@ int exact_pair_call(cms_handle* h, const int64_t* r1, int64_t n1, const int64_t*
 // outputs laid out as top_k_rows' (entries past a count are not written)
 int exact_top_k_rows(cms_handle* h, const int64_t* rows, int64_t nq, int32_t k, int64_t* d_ids, double* d_scores,
                      int32_t* d_counts);
+// GenericUserBasedRecommender.doEstimatePreference over the raw preferences
+// (the sim == null branch) for a batch of users: user u (owner row
+// user_rows[u]) with the neighbours nb_rows[nb_offsets[u] .. nb_offsets[u + 1])
+// (owner rows, in the caller's order) and the candidate item keys
+// item_keys[item_offsets[u] .. item_offsets[u + 1]); one float per candidate.
+// Host arrays in, host estimates out (blocking); the offsets are validated by
+// the caller.
+int exact_estimate_batch(cms_handle* h, int64_t n, const int64_t* user_rows, const int64_t* nb_offsets,
+                         const int64_t* nb_rows, const int64_t* item_offsets, const int64_t* item_keys,
+                         int32_t use_capper, float cap_min, float cap_max, float* out);
+// the attached CSR's offsets [n + 1] and keys, as the host gave them (they live as long as the model)
+void exact_host_csr(const cms_handle* h, const int64_t** off, const int64_t** keys);
 // ---- cms_f64.hip (CMS_COUNTER_F64) ----
 int f64_ingest_csr(cms_handle* h, const int64_t* d_off, const int64_t* d_key, const float* d_val);
 int f64_ingest_coo_host(cms_handle* h, const int64_t* owner, const int64_t* key, const float* val, int64_t np);

@@ -421,6 +421,51 @@ class SketchTable:
         check(self._lib.cms_exact_most_similar(self._h, int(owner_id), int(k), _ptr(ids), _ptr(sc), ctypes.byref(cnt)))
         return ids[:cnt.value], sc[:cnt.value]
 
+    def exact_estimate_preferences(self, user_id, neighbor_ids, item_keys, capper=None):
+        """doEstimatePreference(user, neighbourhood, item) for every item key
+        over the attached model's raw preferences and the exact cosine (the
+        reference's path for a similarity that is no CosineCM); capper =
+        (min, max) or None.  A batch of one user."""
+        nb = np.ascontiguousarray(neighbor_ids, np.int64).reshape(-1)
+        it = np.ascontiguousarray(item_keys, np.int64).reshape(-1)
+        return self.exact_estimate_preferences_batch([user_id], [0, nb.size], nb, [0, it.size], it, capper)
+
+    def exact_estimate_preferences_batch(self, user_ids, nb_offsets, neighbor_ids, item_offsets, item_keys,
+                                         capper=None):
+        """exact_estimate_preferences for many users in one call
+        (cms_exact_estimate_preferences_batch), shaped as
+        estimate_preferences_batch; item keys may repeat, come in any order
+        and be unknown to the model (NaN)."""
+        us, nbo, nb, ito, it = SketchTable._estimate_batch_args(user_ids, nb_offsets, neighbor_ids, item_offsets,
+                                                                item_keys)
+        out = np.zeros(it.size, np.float32)
+        lo, hi = capper if capper is not None else (0.0, 0.0)
+        check(self._lib.cms_exact_estimate_preferences_batch(self._h, us.size, _ptr(us), _ptr(nbo), _ptr(nb),
+                                                             _ptr(ito), _ptr(it), int(capper is not None), float(lo),
+                                                             float(hi), _ptr(out)))
+        return out
+
+    def exact_recommend_batch(self, user_ids, nb_offsets, neighbor_ids, how_many, include_known=False, capper=None):
+        """cms_exact_recommend_batch: GenericUserBasedRecommender.recommend
+        over exact_estimate_preferences for every user of user_ids at once,
+        shaped as recommend_batch with the attached model as the DataModel.
+        Returns (counts [n], items [n][how_many], values [n][how_many] float32)."""
+        us = np.ascontiguousarray(user_ids, np.int64).reshape(-1)
+        nbo = np.ascontiguousarray(nb_offsets, np.int64).reshape(-1)
+        nb = np.ascontiguousarray(neighbor_ids, np.int64).reshape(-1)
+        if nbo.size != us.size + 1 or nbo[0] != 0 or nbo[-1] != nb.size or bool(np.any(np.diff(nbo) < 0)):
+            raise ValueError("nb_offsets must hold len(user_ids) + 1 non-decreasing entries from 0 to len(neighbor_ids)")
+        if how_many < 1:
+            raise ValueError("howMany must be at least 1")
+        counts = np.zeros(us.size, np.int32)
+        items = np.full((us.size, how_many), -1, np.int64)
+        vals = np.full((us.size, how_many), np.nan, np.float32)
+        lo, hi = capper if capper is not None else (0.0, 0.0)
+        check(self._lib.cms_exact_recommend_batch(self._h, us.size, _ptr(us), _ptr(nbo), _ptr(nb), int(how_many),
+                                                  int(bool(include_known)), int(capper is not None), float(lo),
+                                                  float(hi), _ptr(counts), _ptr(items), _ptr(vals)))
+        return counts, items, vals
+
     # -- anonymous profiles: preferences that are no row of the table --
     @staticmethod
     def _profile(keys, vals):
@@ -491,12 +536,9 @@ class SketchTable:
         check(self._lib.cms_anonymous_batch(self._h, int(elem_bytes), ctypes.byref(b)))
         return b.value
 
-    def estimate_preferences_batch(self, user_ids, nb_offsets, neighbor_ids, item_offsets, item_keys, capper=None):
-        """estimate_preferences for many users in one call
-        (cms_estimate_preferences_batch): user u's neighbourhood is
-        neighbor_ids[nb_offsets[u]:nb_offsets[u+1]], its candidates
-        item_keys[item_offsets[u]:item_offsets[u+1]]; returns one float32
-        estimate per candidate."""
+    @staticmethod
+    def _estimate_batch_args(user_ids, nb_offsets, neighbor_ids, item_offsets, item_keys):
+        """The arrays of an estimate batch as contiguous int64, checked."""
         us = np.ascontiguousarray(user_ids, np.int64)
         nbo = np.ascontiguousarray(nb_offsets, np.int64)
         nb = np.ascontiguousarray(neighbor_ids, np.int64)
@@ -510,6 +552,16 @@ class SketchTable:
         for name, o, arr in (("nb_offsets", nbo, nb), ("item_offsets", ito, it)):
             if o[0] != 0 or o[-1] != arr.size or (o.size > 1 and bool(np.any(np.diff(o) < 0))):
                 raise ValueError(f"{name} must start at 0, never decrease and end at the length of its array")
+        return us, nbo, nb, ito, it
+
+    def estimate_preferences_batch(self, user_ids, nb_offsets, neighbor_ids, item_offsets, item_keys, capper=None):
+        """estimate_preferences for many users in one call
+        (cms_estimate_preferences_batch): user u's neighbourhood is
+        neighbor_ids[nb_offsets[u]:nb_offsets[u+1]], its candidates
+        item_keys[item_offsets[u]:item_offsets[u+1]]; returns one float32
+        estimate per candidate."""
+        us, nbo, nb, ito, it = SketchTable._estimate_batch_args(user_ids, nb_offsets, neighbor_ids, item_offsets,
+                                                                item_keys)
         out = np.zeros(it.size, np.float32)
         lo, hi = capper if capper is not None else (0.0, 0.0)
         check(self._lib.cms_estimate_preferences_batch(self._h, us.size, _ptr(us), _ptr(nbo), _ptr(nb), _ptr(ito),

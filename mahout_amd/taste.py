@@ -389,6 +389,36 @@ class CosineCM:
             raise _map_error(e, "user")
         return ids
 
+    def nearestNeighborhoods(self, userIDs, n, dataModel):
+        """NearestNUserNeighborhood(n).getUserNeighborhood for many users:
+        (offsets, neighbour IDs) from one all-owners top-n pass (cms_top_k_all:
+        the same lists as mostSimilarUserIDs, each unordered pair scored once)."""
+        ids, _, cnt = self._table.top_k_all(n)
+        owners = dataModel.getUserIDs()
+        users = np.ascontiguousarray(userIDs, np.int64)
+        rows = np.searchsorted(owners, users)
+        if np.any(rows >= owners.size) or np.any(owners[np.minimum(rows, owners.size - 1)] != users):
+            bad = users[(rows >= owners.size) | (owners[np.minimum(rows, owners.size - 1)] != users)][0]
+            raise NoSuchUserException(int(bad))
+        c = cnt[rows].astype(np.int64)
+        off = np.zeros(users.size + 1, np.int64)
+        np.cumsum(c, out=off[1:])
+        sel = ids[rows]
+        nb = sel[np.arange(n)[None, :] < c[:, None]]
+        return off, np.ascontiguousarray(nb, np.int64)
+
+    def estimatePreferences(self, theUserID, theNeighborhood, itemIDs, capper=None):
+        """doEstimatePreference(user, neighbourhood, item) per item with the
+        sketch point query (GenericUserBasedRecommender.java:153-158)."""
+        return self._table.estimate_preferences(theUserID, theNeighborhood, itemIDs, capper)
+
+    def recommendBatch(self, userIDs, nb_offsets, neighborIDs, modelCSR, howMany, includeKnownItems=False, capper=None):
+        """recommend for many users (cms_recommend_batch) over the DataModel
+        modelCSR = (user IDs ascending, offsets, item IDs): (counts, items, values)."""
+        mu, po, pi = modelCSR
+        return self._table.recommend_batch(userIDs, nb_offsets, neighborIDs, mu, po, pi, howMany, includeKnownItems,
+                                           capper)
+
     def getExportedCMProfileEstimate(self, userID, itemID):
         """DoubleCountMinSketch.get(itemID) on userID's sketch, the point query
         GenericUserBasedRecommender.doEstimatePreference uses (:153-158)."""
@@ -502,6 +532,30 @@ class CosineSimilarity:
             raise _map_error(e, "user")
         return ids
 
+    def nearestNeighborhoods(self, userIDs, n, dataModel):
+        """NearestNUserNeighborhood(n).getUserNeighborhood for many users:
+        (offsets, neighbour IDs), the lists of exact_top_k_rows over the
+        users' owner rows (the same lists as mostSimilarUserIDs)."""
+        users = np.ascontiguousarray(userIDs, np.int64).reshape(-1)
+        try:
+            ids, _, cnt = self._table.exact_top_k_rows(self._table.owner_rows(users), n)
+        except _lib.CmsError as e:
+            raise _map_error(e, "user")
+        c = cnt.astype(np.int64)
+        off = np.zeros(users.size + 1, np.int64)
+        np.cumsum(c, out=off[1:])
+        return off, np.ascontiguousarray(ids[np.arange(n)[None, :] < c[:, None]], np.int64)
+
+    def estimatePreferences(self, theUserID, theNeighborhood, itemIDs, capper=None):
+        """doEstimatePreference(user, neighbourhood, item) per item with the
+        DataModel's own preference values (GenericUserBasedRecommender.java:159-161)."""
+        return self._table.exact_estimate_preferences(theUserID, theNeighborhood, itemIDs, capper)
+
+    def recommendBatch(self, userIDs, nb_offsets, neighborIDs, modelCSR, howMany, includeKnownItems=False, capper=None):
+        """recommend for many users (cms_exact_recommend_batch): the attached
+        model is the DataModel, modelCSR is not read.  (counts, items, values)."""
+        return self._table.exact_recommend_batch(userIDs, nb_offsets, neighborIDs, howMany, includeKnownItems, capper)
+
     def refresh(self, alreadyRefreshed=None):
         """Refreshable.refresh: the attached model is the DataModel's again."""
         try:
@@ -530,23 +584,10 @@ class NearestNUserNeighborhood:
         return self._sim.mostSimilarUserIDs(userID, self.n)
 
     def getUserNeighborhoods(self, userIDs):
-        """getUserNeighborhood for many users: (offsets, neighbour IDs) from
-        one all-owners top-n pass (cms_top_k_all: the same lists as
-        mostSimilarUserIDs, each unordered pair scored once)."""
-        table = self._sim.table
-        ids, _, cnt = table.top_k_all(self.n)
-        owners = self._model.getUserIDs()
-        users = np.ascontiguousarray(userIDs, np.int64)
-        rows = np.searchsorted(owners, users)
-        if np.any(rows >= owners.size) or np.any(owners[np.minimum(rows, owners.size - 1)] != users):
-            bad = users[(rows >= owners.size) | (owners[np.minimum(rows, owners.size - 1)] != users)][0]
-            raise NoSuchUserException(int(bad))
-        c = cnt[rows].astype(np.int64)
-        off = np.zeros(users.size + 1, np.int64)
-        np.cumsum(c, out=off[1:])
-        sel = ids[rows]
-        nb = sel[np.arange(self.n)[None, :] < c[:, None]]
-        return off, np.ascontiguousarray(nb, np.int64)
+        """getUserNeighborhood for many users: (offsets, neighbour IDs), the
+        same lists as mostSimilarUserIDs, from the similarity's one device
+        pass (CosineCM: cms_top_k_all; CosineSimilarity: cms_exact_top_k_rows)."""
+        return self._sim.nearestNeighborhoods(userIDs, self.n, self._model)
 
 
 class ThresholdUserNeighborhood:
@@ -601,10 +642,13 @@ class ThresholdUserNeighborhood:
 
 
 class GenericUserBasedRecommender:
-    """GenericUserBasedRecommender(model, neighborhood, CosineCM): the
-    estimate path with the sketch point query
-    (T/impl/recommender/GenericUserBasedRecommender.java:108-116, 134-184),
-    capped by EstimatedPreferenceCapper when the model has min/max (:209-216)."""
+    """GenericUserBasedRecommender(model, neighborhood, similarity)
+    (T/impl/recommender/GenericUserBasedRecommender.java:108-116, 134-184):
+    with a CosineCM the estimate path with the sketch point query, with a
+    CosineSimilarity the one over the DataModel's own values (sim == null),
+    capped by EstimatedPreferenceCapper when the model has min/max (:209-216).
+    The similarity serves the neighbourhoods, the estimates and the batch
+    recommend (nearestNeighborhoods, estimatePreferences, recommendBatch)."""
 
     def __init__(self, dataModel, neighborhood, similarity):
         self._model = dataModel
@@ -626,7 +670,7 @@ class GenericUserBasedRecommender:
         if theUserID == PlusAnonymousUserDataModel.TEMP_USER_ID and isinstance(self._model, PlusAnonymousUserDataModel):
             return self._sim.anonymousEstimates(theNeighborhood, itemIDs, self._capper)
         try:
-            return self._sim.table.estimate_preferences(theUserID, theNeighborhood, itemIDs, self._capper)
+            return self._sim.estimatePreferences(theUserID, theNeighborhood, itemIDs, self._capper)
         except _lib.CmsError as e:
             raise _map_error(e, "user")
 
@@ -665,18 +709,18 @@ class GenericUserBasedRecommender:
 
     def recommend_all(self, userIDs, howMany, includeKnownItems=False):
         """recommend(userID, howMany) for every user of userIDs in one native
-        call (cms_recommend_batch): the neighbourhoods from one all-owners
-        top-n pass, the candidates in FastIDSet order and TopItems.getTopItems
-        on the host side of the library, every estimate in one device batch.
+        call (cms_recommend_batch, or cms_exact_recommend_batch over a
+        CosineSimilarity): the neighbourhoods from one device pass, the
+        candidates in FastIDSet order and TopItems.getTopItems on the host
+        side of the library, every estimate in one device batch.
         Returns one [(itemID, float value)] list per user, equal to recommend()."""
         if howMany < 1:
             raise ValueError("howMany must be at least 1")
         users = np.ascontiguousarray(userIDs, np.int64)
         nb_off, nb = self._nb.getUserNeighborhoods(users)
-        mu, po, pi = self._model_csr()
         try:
-            cnt, items, vals = self._sim.table.recommend_batch(users, nb_off, nb, mu, po, pi, howMany,
-                                                               includeKnownItems, self._capper)
+            cnt, items, vals = self._sim.recommendBatch(users, nb_off, nb, self._model_csr(), howMany,
+                                                        includeKnownItems, self._capper)
         except _lib.CmsError as e:
             raise _map_error(e, "user")
         return [[(int(items[u, j]), vals[u, j]) for j in range(int(cnt[u]))] for u in range(users.size)]
