@@ -125,7 +125,10 @@ int cms_shape_from_delta_epsilon(double delta, double epsilon, int32_t* width, i
  *   CMS_THRESHOLD_SLAB_ROWS=<rows>  query rows per slab of cms_threshold_neighbors, rounded up to
  *                         whole 128-row tiles (default: the top-k's slab budget)
  *   CMS_EXACT_TILE=<rows> candidate rows per workgroup of the exact cosine's tile kernel, rounded up
- *                         to a multiple of 64 (default and most: 8192, 64 KiB of LDS cells) */
+ *                         to a multiple of 64 (default and most: 8192, 64 KiB of LDS cells)
+ *   CMS_COMMON_TILE=<n>   candidates per workgroup of the co-rated similarities' tile kernel, rounded
+ *                         up to a multiple of 64 (default and most, by measure: 5440 Euclidean,
+ *                         2304 uncentered cosine, 1472 Pearson -- just under 64 KiB of LDS cells) */
 int cms_create(const cms_params* p, cms_handle** out);
 void cms_destroy(cms_handle* h);
 const char* cms_last_error(void);
@@ -858,6 +861,48 @@ int cms_exact_recommend_batch(cms_handle* h, int64_t n, const int64_t* user_ids,
                               const int64_t* neighbor_ids, int32_t how_many, int32_t include_known, int32_t use_capper,
                               float cap_min, float cap_max, int32_t* out_counts, int64_t* out_items,
                               float* out_values);
+
+/* ---- the co-rated similarities ---------------------------------------------------
+ * AbstractSimilarity.userSimilarity / itemSimilarity over the attached model
+ * (cms_exact_attach_csr): at each key two preference lists have in COMMON, in
+ * ascending order, the reference's six sequential fp64 sums (sumXY, sumX,
+ * sumX2, sumY, sumY2, sumXYdiff2) and the count; NaN when either list is
+ * empty; then the measure's ending
+ *   CMS_SIM_UNCENTERED_COSINE  UncenteredCosineSimilarity.computeResult -- the
+ *                              text of CosineCM.computeResult, so on
+ *                              CMS_SIDE_KEY this is the reference's
+ *                              CosineCM.itemSimilarity;
+ *   CMS_SIM_PEARSON            PearsonCorrelationSimilarity (centred sums);
+ *   CMS_SIM_EUCLIDEAN          EuclideanDistanceSimilarity;
+ * and, for a non-NaN result, normalizeWeightResult(result, count, num) under
+ * the handle's weighting with count the number of common entries and num the
+ * model's distinct keys (CMS_SIDE_OWNER) or its rows (CMS_SIDE_KEY).  A pair
+ * with no common entry is NaN.  Every result equals the reference's bit for
+ * bit.  On CMS_SIDE_OWNER the lists are the owners' and IDs are owner IDs; on
+ * CMS_SIDE_KEY the lists are the keys' posting lists (the model's items over
+ * their users) and IDs are the attached keys.  CMS_E_STATE without a model,
+ * CMS_E_PARAM for an unknown measure or side, CMS_E_NO_SUCH_ID for an unknown
+ * ID, before anything is written.  Works on every handle kind, before or after
+ * cms_finalize; the sketch table is neither read nor written. */
+#define CMS_SIM_UNCENTERED_COSINE 0
+#define CMS_SIM_PEARSON 1
+#define CMS_SIM_EUCLIDEAN 2
+#define CMS_SIDE_OWNER 0
+#define CMS_SIDE_KEY 1
+/* out[t] = similarity(id1, ids2[t]).  Timing scope "common_pairs". */
+int cms_common_similarities(cms_handle* h, int32_t measure, int32_t side, int64_t id1, const int64_t* ids2, int64_t m,
+                            double* out);
+/* out[t] = similarity(ids1[t], ids2[t]). */
+int cms_common_pairs(cms_handle* h, int32_t measure, int32_t side, const int64_t* ids1, const int64_t* ids2, int64_t m,
+                     double* out);
+/* The k most similar of the side's lists for each ID ids[q] (any order, repeats
+ * allowed), laid out and ordered as cms_exact_top_k_rows: NaN skipped, the
+ * query itself excluded, similarity descending then row / key ascending;
+ * out_ids / out_scores [nq][k] (padding: ID -1, NaN), out_counts [nq];
+ * out_scores may be NULL.  k in [1, 512].  Timing scopes "common_tile",
+ * "common_pairs", "top_k". */
+int cms_common_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* ids, int64_t nq, int32_t k,
+                     int64_t* out_ids, double* out_scores, int32_t* out_counts);
 
 /* ---- instrumentation ------------------------------------------------------- */
 typedef struct cms_stats {

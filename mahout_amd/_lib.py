@@ -59,6 +59,7 @@ EXPORTS = [
     "cms_exact_attach_csr", "cms_exact_detach", "cms_exact_similarities", "cms_exact_pairs", "cms_exact_top_k_rows",
     "cms_exact_most_similar", "cms_owner_rows",
     "cms_exact_estimate_preferences_batch", "cms_exact_recommend_batch",
+    "cms_common_similarities", "cms_common_pairs", "cms_common_top_k",
 ]
 
 
@@ -217,6 +218,9 @@ _SIGS = {
                                                     ctypes.c_float, _vp]),
     "cms_exact_recommend_batch": (_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _int, ctypes.c_float, ctypes.c_float,
                                          _vp, _vp, _vp]),
+    "cms_common_similarities": (_int, [_vp, _i32, _i32, _i64, _vp, _i64, _vp]),
+    "cms_common_pairs": (_int, [_vp, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "cms_common_top_k": (_int, [_vp, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -40,7 +40,9 @@
 #include <thread>
 #include <vector>
 
+#include "cms_common.h"
 #include "cms_exact.h"
+#include "cms_exact_model.h"
 #include "cms_exact_plan.h"
 #include "cms_internal.h"
 #include "cms_ref.h"
@@ -51,21 +53,6 @@ constexpr int kExactThreads = 512;      // 8 waves; two workgroups per CU at the
 constexpr int kExactPairThreads = 256;
 constexpr int kExactEstThreads = 256;   // three workgroups per CU at the default tile (48 KiB each)
 constexpr int64_t kExactChunkMax = 16384;  // query rows per slab chunk (the tile grid is chunk x tiles)
-
-struct ExactModel {
-  int64_t n = 0, npairs = 0, nitems = 0;
-  int shift = kExactNoShift;
-  std::vector<uint8_t> h_seq;  // [n] 1: not integer-eligible
-  std::vector<int64_t> ids;    // [nitems] getItemIDs(): the keys, sorted and unique (key -> dense item index)
-  std::vector<int64_t> h_off, h_keys;  // the attached CSR's offsets and keys: the DataModel of the recommend call
-  int64_t n_seq = 0;
-  DevBuf off, item, val, unit;  // owner side: [n + 1] i64, [np] dense item (i32), float, unit (i32)
-  DevBuf ioff, irow, iunit;     // item side: [nitems + 1] i64, [np] owner row ascending (i32), unit (i32)
-  DevBuf U, root;               // [n] saturating sum of squared units (u64), Math.sqrt(sumX2) (f64)
-  DevBuf seq_rows;              // [n_seq] the non-eligible rows (i64)
-  DevBuf q1, q2, sel, out;      // a call's rows, selected queries and results
-  DevBuf e_urow, e_nboff, e_slot, e_tiles, e_est;  // an estimate batch: users' rows, neighbour offsets, plan, estimates
-};
 
 struct ExactView {
   const int64_t* off;
@@ -281,18 +268,6 @@ void exact_release(cms_handle* h) {
 
 static int exact_tile_rows(const cms_handle* h) { return exact_tile_for(h->tune.exact_tile); }
 
-// (the host array must stay alive until the stream is synchronised)
-template <class T>
-static int upload(cms_handle* h, DevBuf& b, const T* v, size_t count) {
-  CMS_HIP(b.ensure(sizeof(T) * count));
-  if (count > 0) CMS_HIP(hipMemcpyAsync(b.ptr, v, sizeof(T) * count, hipMemcpyHostToDevice, h->stream));
-  return CMS_OK;
-}
-template <class T>
-static int upload(cms_handle* h, DevBuf& b, const std::vector<T>& v) {
-  return upload(h, b, v.data(), v.size());
-}
-
 int exact_attach(cms_handle* h, const int64_t* off, const int64_t* keys, const float* vals) {
   const int64_t n = h->n;
   if (!exact_valid_csr(n, off, keys))
@@ -325,6 +300,13 @@ int exact_attach(cms_handle* h, const int64_t* off, const int64_t* keys, const f
   std::vector<int64_t> seq_rows;
   m->h_seq.assign((size_t)n, 0);
   std::vector<int32_t> irow((size_t)np), iunit((size_t)np);
+  // the co-rated similarities' share (cms_common.hip): the floats in posting-list
+  // order, the items' U, and per side the lists at or above kCommonEligible
+  std::vector<float> ival((size_t)np);
+  std::vector<uint64_t> iU((size_t)m->nitems, m->shift == kExactNoShift ? ~0ULL : 0ULL);
+  std::vector<int64_t> cseq[2];
+  m->h_cseq[0].assign((size_t)n, 0);
+  m->h_cseq[1].assign((size_t)m->nitems, 0);
   {
     std::vector<int64_t> fill(ioff.begin(), ioff.end() - 1);
     for (int64_t r = 0; r < n; ++r) {  // rows in ascending order: every posting list ascends
@@ -334,13 +316,28 @@ int exact_attach(cms_handle* h, const int64_t* off, const int64_t* keys, const f
         m->h_seq[(size_t)r] = 1;
         seq_rows.push_back(r);
       }
+      if (U[(size_t)r] >= kCommonEligible) {
+        m->h_cseq[0][(size_t)r] = 1;
+        cseq[0].push_back(r);
+      }
       for (int64_t t = off[r]; t < off[r + 1]; ++t) {
         const int64_t at = fill[(size_t)item[(size_t)t]]++;
         irow[(size_t)at] = (int32_t)r;
         iunit[(size_t)at] = unit[(size_t)t];
+        ival[(size_t)at] = vals[t];
+        uint64_t& u = iU[(size_t)item[(size_t)t]];
+        const uint64_t sq = (uint64_t)((int64_t)unit[(size_t)t] * unit[(size_t)t]);  // < 2^62
+        u = u + sq < u ? ~0ULL : u + sq;
       }
     }
+    for (int64_t i = 0; i < m->nitems; ++i)
+      if (iU[(size_t)i] >= kCommonEligible) {
+        m->h_cseq[1][(size_t)i] = 1;
+        cseq[1].push_back(i);
+      }
   }
+  m->n_cseq[0] = (int64_t)cseq[0].size();
+  m->n_cseq[1] = (int64_t)cseq[1].size();
   m->n_seq = (int64_t)seq_rows.size();
   m->h_off.assign(off, off + n + 1);
   m->h_keys.assign(keys, keys + np);
@@ -351,7 +348,9 @@ int exact_attach(cms_handle* h, const int64_t* off, const int64_t* keys, const f
     (void)((rc = upload(h, m->off, off, (size_t)n + 1)) || (rc = upload(h, m->val, vals, (size_t)np)) ||
            (rc = upload(h, m->item, item)) || (rc = upload(h, m->unit, unit)) || (rc = upload(h, m->ioff, ioff)) ||
            (rc = upload(h, m->irow, irow)) || (rc = upload(h, m->iunit, iunit)) || (rc = upload(h, m->U, U)) ||
-           (rc = upload(h, m->root, root)) || (rc = upload(h, m->seq_rows, seq_rows)));
+           (rc = upload(h, m->root, root)) || (rc = upload(h, m->seq_rows, seq_rows)) ||
+           (rc = upload(h, m->ival, ival)) || (rc = upload(h, m->iU, iU)) || (rc = upload(h, m->d_ids, m->ids)) ||
+           (rc = upload(h, m->cseq[0], cseq[0])) || (rc = upload(h, m->cseq[1], cseq[1])));
   }
   const hipError_t synced = hipStreamSynchronize(h->stream);  // whatever was queued is done with the host arrays
   if (rc) return rc;

@@ -1,0 +1,47 @@
+// cms_exact_model.h -- the attached DataModel of a handle (exact_attach,
+// cms_exact.hip), as the files that score over it see it: cms_exact.hip (the
+// full-norm cosine) and cms_common.hip (the co-rated similarities).
+#pragma once
+#include <vector>
+
+#include "cms_exact.h"
+#include "cms_internal.h"
+
+namespace cms {
+
+struct ExactModel {
+  int64_t n = 0, npairs = 0, nitems = 0;
+  int shift = kExactNoShift;
+  std::vector<uint8_t> h_seq;  // [n] 1: not integer-eligible
+  std::vector<int64_t> ids;    // [nitems] getItemIDs(): the keys, sorted and unique (key -> dense item index)
+  std::vector<int64_t> h_off, h_keys;  // the attached CSR's offsets and keys: the DataModel of the recommend call
+  int64_t n_seq = 0;
+  DevBuf off, item, val, unit;  // owner side: [n + 1] i64, [np] dense item (i32), float, unit (i32)
+  DevBuf ioff, irow, iunit;     // item side: [nitems + 1] i64, [np] owner row ascending (i32), unit (i32)
+  DevBuf U, root;               // [n] saturating sum of squared units (u64), Math.sqrt(sumX2) (f64)
+  DevBuf seq_rows;              // [n_seq] the non-eligible rows (i64)
+  DevBuf q1, q2, sel, out;      // a call's rows, selected queries and results
+  DevBuf e_urow, e_nboff, e_slot, e_tiles, e_est;  // an estimate batch: users' rows, neighbour offsets, plan, estimates
+  // the co-rated similarities (cms_common.hip): the floats in posting-list
+  // order, the items' U over their posting lists, the item keys on the device
+  // (the top-k's IDs on the key side), and per side the lists that are not
+  // common-eligible (U >= 2^51): host flags and the device list
+  DevBuf ival, iU, d_ids;       // [np] float, [nitems] u64, [nitems] i64
+  std::vector<uint8_t> h_cseq[2];  // [n], [nitems]
+  DevBuf cseq[2];                  // i64 indices, ascending
+  int64_t n_cseq[2] = {0, 0};
+};
+
+// (the host array must stay alive until the stream is synchronised)
+template <class T>
+inline int upload(cms_handle* h, DevBuf& b, const T* v, size_t count) {
+  CMS_HIP(b.ensure(sizeof(T) * count));
+  if (count > 0) CMS_HIP(hipMemcpyAsync(b.ptr, v, sizeof(T) * count, hipMemcpyHostToDevice, h->stream));
+  return CMS_OK;
+}
+template <class T>
+inline int upload(cms_handle* h, DevBuf& b, const std::vector<T>& v) {
+  return upload(h, b, v.data(), v.size());
+}
+
+}  // namespace cms

@@ -231,6 +231,7 @@ struct Tunables {
   int64_t threshold_slab_rows = 0;  // CMS_THRESHOLD_SLAB_ROWS: query rows per chunk of threshold_rows (0: slab_rows_for)
   int exact_tile = 0;       // CMS_EXACT_TILE: candidate rows per workgroup of k_exact_tile, a multiple of 64 (0: kExactTile)
   int exact_est_tile = 0;   // CMS_EXACT_EST_TILE: candidate slots per workgroup of k_exact_estimate, a multiple of 64 (0: kExactEstTile)
+  int common_tile = 0;      // CMS_COMMON_TILE: candidates per workgroup of k_common_tile, a multiple of 64 (0: the measure's default)
 };
 struct ExactModel;  // the attached DataModel of the exact cosine (cms_exact.hip)
 }  // namespace cms
@@ -681,8 +682,11 @@ struct TopQuery {
   int64_t self_col;  // slab column of the query itself (excluded)
   int64_t out_pos;   // output slot
 };
+// (ncols > 0: the slab has ncols columns, ld = ncols, whose IDs are d_col_ids -- the column index when null;
+// else the owners and their IDs)
 int launch_top_k(cms_handle* h, const double* slab, const std::vector<TopQuery>& qs, int32_t k, const int64_t* d_perm,
-                 int64_t* d_ids, double* d_scores, int32_t* d_counts);
+                 int64_t* d_ids, double* d_scores, int32_t* d_counts, int64_t ncols = 0,
+                 const int64_t* d_col_ids = nullptr);
 int64_t slab_rows_for(int64_t n);
 // ---- cms_threshold.hip: every owner at or above a similarity ----
 // ThresholdUserNeighborhood lists of the owner rows rows[0, nq) (any order,
@@ -740,6 +744,17 @@ int exact_estimate_batch(cms_handle* h, int64_t n, const int64_t* user_rows, con
                          int32_t use_capper, float cap_min, float cap_max, float* out);
 // the attached CSR's offsets [n + 1] and keys, as the host gave them (they live as long as the model)
 void exact_host_csr(const cms_handle* h, const int64_t** off, const int64_t** keys);
+// ---- cms_common.hip: the co-rated similarities over the attached DataModel ----
+// (h->exact is non-null; measure and side are validated by the caller: CMS_SIM_*, CMS_SIDE_*)
+// the index of an ID on a side: the owner row is the caller's; here the dense item index of a key
+int common_key_index(cms_handle* h, int64_t key, int64_t* index);
+// host indices in, host results out (blocking), shaped as exact_pair_call
+int common_pair_call(cms_handle* h, int32_t measure, int32_t side, const int64_t* i1, int64_t n1, const int64_t* i2,
+                     int64_t n2, bool cross, double* out);
+// the k most similar of the side's lists for the indices idx[0, nq) (host) into device outputs laid out as
+// top_k_rows'; the IDs are owner IDs or item keys
+int common_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* idx, int64_t nq, int32_t k,
+                 int64_t* d_ids, double* d_scores, int32_t* d_counts);
 // ---- cms_f64.hip (CMS_COUNTER_F64) ----
 int f64_ingest_csr(cms_handle* h, const int64_t* d_off, const int64_t* d_key, const float* d_val);
 int f64_ingest_coo_host(cms_handle* h, const int64_t* owner, const int64_t* key, const float* val, int64_t np);

@@ -368,19 +368,22 @@ __global__ __launch_bounds__(kTopThreads) void k_top_k_fast(const double* slab, 
 }
 
 int launch_top_k(cms_handle* h, const double* slab, const std::vector<TopQuery>& qs, int32_t k,
-                        const int64_t* d_perm, int64_t* d_ids, double* d_scores, int32_t* d_counts) {
+                        const int64_t* d_perm, int64_t* d_ids, double* d_scores, int32_t* d_counts, int64_t ncols,
+                        const int64_t* d_col_ids) {
   if (qs.empty()) return CMS_OK;
+  const int64_t n = ncols > 0 ? ncols : h->n;  // the slab's columns and their IDs: the owners unless told otherwise
+  const int64_t* col_ids = ncols > 0 ? d_col_ids : h->d_owner_ids;
   CMS_HIP(h->ws_topq.ensure(sizeof(TopQuery) * qs.size()));
   CMS_HIP(hipMemcpyAsync(h->ws_topq.ptr, qs.data(), sizeof(TopQuery) * qs.size(), hipMemcpyHostToDevice, h->stream));
-  const bool fast = h->n < (int64_t(1) << 32);  // candidate rows/columns held as u32
+  const bool fast = n < (int64_t(1) << 32);  // candidate rows/columns held as u32
   {
     TimedScope ts(h, "top_k");
     if (fast)
-      hipLaunchKernelGGL(k_top_k_fast, dim3((unsigned)qs.size()), dim3(kTopThreads), 0, h->stream, slab, h->n, h->n,
-                         k, h->ws_topq.as<TopQuery>(), d_perm, h->d_owner_ids, d_ids, d_scores, d_counts);
+      hipLaunchKernelGGL(k_top_k_fast, dim3((unsigned)qs.size()), dim3(kTopThreads), 0, h->stream, slab, n, n,
+                         k, h->ws_topq.as<TopQuery>(), d_perm, col_ids, d_ids, d_scores, d_counts);
     else
-      hipLaunchKernelGGL(k_top_k, dim3((unsigned)qs.size()), dim3(kTopThreads), 0, h->stream, slab, h->n, h->n, k,
-                         h->ws_topq.as<TopQuery>(), d_perm, h->d_owner_ids, d_ids, d_scores, d_counts);
+      hipLaunchKernelGGL(k_top_k, dim3((unsigned)qs.size()), dim3(kTopThreads), 0, h->stream, slab, n, n, k,
+                         h->ws_topq.as<TopQuery>(), d_perm, col_ids, d_ids, d_scores, d_counts);
     CMS_HIP(hipGetLastError());
   }
   if (fast) {  // rows the sampled threshold missed go through the radix select
@@ -399,8 +402,8 @@ int launch_top_k(cms_handle* h, const double* slab, const std::vector<TopQuery>&
       CMS_HIP(hipMemcpyAsync(h->ws_topq.ptr, redo.data(), sizeof(TopQuery) * redo.size(), hipMemcpyHostToDevice,
                              h->stream));
       TimedScope ts(h, "top_k");
-      hipLaunchKernelGGL(k_top_k, dim3((unsigned)redo.size()), dim3(kTopThreads), 0, h->stream, slab, h->n, h->n, k,
-                         h->ws_topq.as<TopQuery>(), d_perm, h->d_owner_ids, d_ids, d_scores, d_counts);
+      hipLaunchKernelGGL(k_top_k, dim3((unsigned)redo.size()), dim3(kTopThreads), 0, h->stream, slab, n, n, k,
+                         h->ws_topq.as<TopQuery>(), d_perm, col_ids, d_ids, d_scores, d_counts);
       CMS_HIP(hipGetLastError());
     }
   }

@@ -466,6 +466,49 @@ class SketchTable:
                                                   float(hi), _ptr(counts), _ptr(items), _ptr(vals)))
         return counts, items, vals
 
+    # -- the co-rated similarities over the attached DataModel --
+    COMMON_MEASURES = {"uncentered_cosine": 0, "pearson": 1, "euclidean": 2}  # CMS_SIM_*
+    COMMON_SIDES = {"owner": 0, "key": 1}  # CMS_SIDE_*
+
+    @classmethod
+    def _common_args(cls, measure, side):
+        """measure / side by name, or as the C values (an unknown integer is the library's CMS_E_PARAM)."""
+        return (int(cls.COMMON_MEASURES.get(measure, measure)), int(cls.COMMON_SIDES.get(side, side)))
+
+    def common_similarities(self, id1, ids2, measure="pearson", side="owner"):
+        """AbstractSimilarity.userSimilarity (side="owner", owner IDs) or
+        itemSimilarity (side="key", the attached keys) of id1 with every
+        ids2[t] under measure: "uncentered_cosine", "pearson" or "euclidean",
+        over the entries the two lists have in common (cms_common_similarities)."""
+        ids2 = np.ascontiguousarray(ids2, np.int64).reshape(-1)
+        out = np.zeros(ids2.size, np.float64)
+        ms, sd = self._common_args(measure, side)
+        check(self._lib.cms_common_similarities(self._h, ms, sd, int(id1), _ptr(ids2), ids2.size, _ptr(out)))
+        return out
+
+    def common_pairs(self, ids1, ids2, measure="pearson", side="owner"):
+        """similarity(ids1[t], ids2[t]), element-wise (cms_common_pairs)."""
+        ids1 = np.ascontiguousarray(ids1, np.int64).reshape(-1)
+        ids2 = np.ascontiguousarray(ids2, np.int64).reshape(-1)
+        if ids1.size != ids2.size:
+            raise ValueError("ids1 and ids2 differ in length")
+        out = np.zeros(ids1.size, np.float64)
+        ms, sd = self._common_args(measure, side)
+        check(self._lib.cms_common_pairs(self._h, ms, sd, _ptr(ids1), _ptr(ids2), ids1.size, _ptr(out)))
+        return out
+
+    def common_top_k(self, ids, k, measure="pearson", side="owner"):
+        """The k most similar owners (or keys) of each ID under measure
+        (cms_common_top_k): ids [nq][k], scores [nq][k] (padding: ID -1, NaN)
+        and counts [nq], ordered as exact_top_k_rows orders them."""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        out = np.zeros((ids.size, k), np.int64)
+        sc = np.zeros((ids.size, k), np.float64)
+        cnt = np.zeros(ids.size, np.int32)
+        ms, sd = self._common_args(measure, side)
+        check(self._lib.cms_common_top_k(self._h, ms, sd, _ptr(ids), ids.size, int(k), _ptr(out), _ptr(sc), _ptr(cnt)))
+        return out, sc, cnt
+
     # -- anonymous profiles: preferences that are no row of the table --
     @staticmethod
     def _profile(keys, vals):

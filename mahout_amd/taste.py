@@ -567,6 +567,89 @@ class CosineSimilarity:
         self._table.close()
 
 
+class _CommonSimilarity(CosineSimilarity):
+    """AbstractSimilarity's co-rated measures over the DataModel on the GPU
+    (cms_common_*), with the reference's values bit for bit: the sums run over
+    the items two users have in common (userSimilarity) or the users two items
+    have in common (itemSimilarity -- items of the same model, the reference's
+    own meaning), and normalizeWeightResult takes count = the common entries,
+    num = getNumItems() or getNumUsers().  A pair with nothing in common is
+    NaN.  The handle, refresh and close are CosineSimilarity's.
+
+    The neighbourhoods are served (nearestNeighborhoods, so
+    NearestNUserNeighborhood works unchanged); the device estimate and batch
+    recommend of GenericUserBasedRecommender are not: the library's estimate
+    batch forms its similarities with the full-norm cosine."""
+
+    MEASURE = None
+
+    def _similarities(self, side, kind, id1, ids2):
+        try:
+            return self._table.common_similarities(id1, ids2, self.MEASURE, side)
+        except _lib.CmsError as e:
+            raise _map_error(e, kind)
+
+    def userSimilarity(self, userID1, userID2):
+        return float(self._similarities("owner", "user", userID1, [userID2])[0])
+
+    def userSimilarities(self, userID1, userID2s):
+        return self._similarities("owner", "user", userID1, userID2s)
+
+    def itemSimilarity(self, itemID1, itemID2):
+        return float(self._similarities("key", "item", itemID1, [itemID2])[0])
+
+    def itemSimilarities(self, itemID1, itemID2s):
+        return self._similarities("key", "item", itemID1, itemID2s)
+
+    def allSimilarItemIDs(self, itemID):
+        """AbstractItemSimilarity.allSimilarItemIDs (:48-58) over the model's items."""
+        ids = np.asarray(self._model.getItemIDs(), np.int64)
+        return ids[~np.isnan(self.itemSimilarities(itemID, ids))]
+
+    def _top(self, userIDs, k):
+        try:
+            return self._table.common_top_k(userIDs, k, self.MEASURE, "owner")
+        except _lib.CmsError as e:
+            raise _map_error(e, "user")
+
+    def mostSimilarUserIDs(self, userID, howMany):
+        if howMany < 1:
+            raise ValueError("howMany must be at least 1")
+        ids, _, cnt = self._top([userID], howMany)
+        return ids[0, :int(cnt[0])]
+
+    def nearestNeighborhoods(self, userIDs, n, dataModel):
+        users = np.ascontiguousarray(userIDs, np.int64).reshape(-1)
+        ids, _, cnt = self._top(users, n)
+        c = cnt.astype(np.int64)
+        off = np.zeros(users.size + 1, np.int64)
+        np.cumsum(c, out=off[1:])
+        return off, np.ascontiguousarray(ids[np.arange(n)[None, :] < c[:, None]], np.int64)
+
+    def estimatePreferences(self, theUserID, theNeighborhood, itemIDs, capper=None):
+        raise NotImplementedError("the device estimate takes its similarities from the full-norm cosine only")
+
+    def recommendBatch(self, userIDs, nb_offsets, neighborIDs, modelCSR, howMany, includeKnownItems=False, capper=None):
+        raise NotImplementedError("the device batch recommend takes its similarities from the full-norm cosine only")
+
+
+class PearsonCorrelationSimilarity(_CommonSimilarity):
+    """PearsonCorrelationSimilarity(DataModel[, Weighting]) (T/impl/similarity/PearsonCorrelationSimilarity.java)."""
+    MEASURE = "pearson"
+
+
+class UncenteredCosineSimilarity(_CommonSimilarity):
+    """UncenteredCosineSimilarity(DataModel[, Weighting]) (T/impl/similarity/UncenteredCosineSimilarity.java).
+    Its itemSimilarity is the value of the reference's CosineCM.itemSimilarity,
+    which CosineCM inherits from AbstractSimilarity with the same computeResult."""
+    MEASURE = "uncentered_cosine"
+
+
+class EuclideanDistanceSimilarity(_CommonSimilarity):
+    """EuclideanDistanceSimilarity(DataModel[, Weighting]) (T/impl/similarity/EuclideanDistanceSimilarity.java)."""
+    MEASURE = "euclidean"
+
+
 class NearestNUserNeighborhood:
     """NearestNUserNeighborhood(n, similarity, model): the n most similar
     users (T/impl/neighborhood/NearestNUserNeighborhood.java) -- TopItems
