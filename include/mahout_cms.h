@@ -128,7 +128,9 @@ int cms_shape_from_delta_epsilon(double delta, double epsilon, int32_t* width, i
  *                         to a multiple of 64 (default and most: 8192, 64 KiB of LDS cells)
  *   CMS_COMMON_TILE=<n>   candidates per workgroup of the co-rated similarities' tile kernel, rounded
  *                         up to a multiple of 64 (default and most, by measure: 5440 Euclidean,
- *                         2304 uncentered cosine, 1472 Pearson -- just under 64 KiB of LDS cells) */
+ *                         2304 uncentered cosine, 1472 Pearson -- just under 64 KiB of LDS cells)
+ *   CMS_SET_TILE=<n>      candidates per workgroup of the set similarities' tile kernel, rounded up
+ *                         to a multiple of 64 (default and most: 16384, 64 KiB of LDS counts) */
 int cms_create(const cms_params* p, cms_handle** out);
 void cms_destroy(cms_handle* h);
 const char* cms_last_error(void);
@@ -903,6 +905,47 @@ int cms_common_pairs(cms_handle* h, int32_t measure, int32_t side, const int64_t
  * "common_pairs", "top_k". */
 int cms_common_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* ids, int64_t nq, int32_t k,
                      int64_t* out_ids, double* out_scores, int32_t* out_counts);
+
+/* ---- the set similarities ----------------------------------------------------------
+ * The reference's measures for preference data without values, over the
+ * attached model (cms_exact_attach_csr; the values are not read): with n1 and
+ * n2 the lengths of two lists of one side, k the number of entries they share
+ * and num the model's distinct keys (CMS_SIDE_OWNER) or its rows
+ * (CMS_SIDE_KEY),
+ *   CMS_SET_COOCCURRENCE   (double)k, NaN when k == 0;
+ *   CMS_SET_TANIMOTO       TanimotoCoefficientSimilarity: on CMS_SIDE_OWNER NaN
+ *                          when both lists are empty and 0.0 when one is; NaN
+ *                          when k == 0, else k / (n1 + n2 - k);
+ *   CMS_SET_CITY_BLOCK     CityBlockSimilarity: 1 / (1 + n1 + n2 - 2k), never
+ *                          NaN, so a top-k ranks every other list;
+ *   CMS_SET_LOGLIKELIHOOD  LogLikelihoodSimilarity: NaN when k == 0, else
+ *                          1 - 1 / (1 + LogLikelihood.logLikelihoodRatio(k,
+ *                          n2 - k, n1 - k, num - n1 - n2 + k)).
+ * No weighting applies: the handle's is not read.  The first three equal the
+ * reference's values bit for bit.  Log-likelihood runs the reference's
+ * operations in the reference's order on exact integers, every one of them
+ * correctly rounded but log, which Java itself specifies to 1 ulp only: the
+ * result lies within 2^-48 S + 2^-52 of that sequence's real value (S the sum
+ * of the absolute values of its eleven x log x terms), and equal (k, n1, n2,
+ * num) give equal bits.  Sides, IDs, argument rules and errors as the co-rated
+ * similarities': CMS_E_STATE without a model, CMS_E_PARAM for an unknown
+ * measure or side, CMS_E_NO_SUCH_ID for an unknown ID, before anything is
+ * written.  Works on every handle kind, before or after cms_finalize; the
+ * sketch table is neither read nor written. */
+#define CMS_SET_COOCCURRENCE 0
+#define CMS_SET_TANIMOTO 1
+#define CMS_SET_CITY_BLOCK 2
+#define CMS_SET_LOGLIKELIHOOD 3
+/* out[t] = similarity(id1, ids2[t]).  Timing scope "set_pairs". */
+int cms_set_similarities(cms_handle* h, int32_t measure, int32_t side, int64_t id1, const int64_t* ids2, int64_t m,
+                         double* out);
+/* out[t] = similarity(ids1[t], ids2[t]). */
+int cms_set_pairs(cms_handle* h, int32_t measure, int32_t side, const int64_t* ids1, const int64_t* ids2, int64_t m,
+                  double* out);
+/* The k most similar of the side's lists for each ID, laid out and ordered as
+ * cms_common_top_k.  Timing scopes "set_tile", "top_k". */
+int cms_set_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* ids, int64_t nq, int32_t k,
+                  int64_t* out_ids, double* out_scores, int32_t* out_counts);
 
 /* ---- instrumentation ------------------------------------------------------- */
 typedef struct cms_stats {

@@ -361,6 +361,7 @@ static int create_impl(const cms_params* p, bool per_owner, cms_handle** out) {
     h->tune.exact_tile = std::max(0, num("CMS_EXACT_TILE", 0));
     h->tune.exact_est_tile = std::max(0, num("CMS_EXACT_EST_TILE", 0));
     h->tune.common_tile = std::max(0, num("CMS_COMMON_TILE", 0));
+    h->tune.set_tile = std::max(0, num("CMS_SET_TILE", 0));
   }
   h->per_owner = per_owner;
   h->f64 = f64;
@@ -1922,6 +1923,64 @@ int cms_common_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t
   CMS_HIP(hipMemsetAsync(o_sc.ptr, 0xFF, sizeof(double) * cells, h->stream));
   CMS_HIP(hipMemsetAsync(o_cnt.ptr, 0, sizeof(int32_t) * (size_t)nq, h->stream));
   if ((rc = common_top_k(h, measure, side, idx.data(), nq, k, o_ids.as<int64_t>(), o_sc.as<double>(), o_cnt.as<int32_t>())))
+    return rc;
+  CMS_HIP(hipMemcpyAsync(out_ids, o_ids.ptr, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, h->stream));
+  if (out_scores) CMS_HIP(hipMemcpyAsync(out_scores, o_sc.ptr, sizeof(double) * cells, hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipMemcpyAsync(out_counts, o_cnt.ptr, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  return CMS_OK;
+}
+
+// ---- the set similarities over the attached DataModel (cms_set.hip) ----
+
+static int set_require(cms_handle* h, const char* what, int32_t measure, int32_t side) {
+  if (measure < CMS_SET_COOCCURRENCE || measure > CMS_SET_LOGLIKELIHOOD)
+    return set_error(CMS_E_PARAM, "%s: unknown measure %d", what, (int)measure);
+  if (side != CMS_SIDE_OWNER && side != CMS_SIDE_KEY) return set_error(CMS_E_PARAM, "%s: unknown side %d", what, (int)side);
+  return exact_require(h, what);
+}
+
+int cms_set_similarities(cms_handle* h, int32_t measure, int32_t side, int64_t id1, const int64_t* ids2, int64_t m,
+                         double* out) {
+  if (!h || m < 0 || (m > 0 && (!ids2 || !out))) return set_error(CMS_E_PARAM, "null argument");
+  Guard g(h);
+  int rc = set_require(h, "cms_set_similarities", measure, side);
+  if (rc) return rc;
+  std::vector<int64_t> q, idx;
+  if ((rc = common_indices(h, side, &id1, 1, q)) || (rc = common_indices(h, side, ids2, m, idx))) return rc;
+  return set_pair_call(h, measure, side, q.data(), 1, idx.data(), m, true, out);
+}
+
+int cms_set_pairs(cms_handle* h, int32_t measure, int32_t side, const int64_t* ids1, const int64_t* ids2, int64_t m,
+                  double* out) {
+  if (!h || m < 0 || (m > 0 && (!ids1 || !ids2 || !out))) return set_error(CMS_E_PARAM, "null argument");
+  Guard g(h);
+  int rc = set_require(h, "cms_set_pairs", measure, side);
+  if (rc) return rc;
+  std::vector<int64_t> i1, i2;
+  if ((rc = common_indices(h, side, ids1, m, i1)) || (rc = common_indices(h, side, ids2, m, i2))) return rc;
+  return set_pair_call(h, measure, side, i1.data(), m, i2.data(), m, false, out);
+}
+
+int cms_set_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* ids, int64_t nq, int32_t k,
+                  int64_t* out_ids, double* out_scores, int32_t* out_counts) {
+  if (!h || nq < 0 || (nq > 0 && (!ids || !out_ids || !out_counts))) return set_error(CMS_E_PARAM, "null argument");
+  if (k < 1 || k > kCandCap / 2) return set_error(CMS_E_PARAM, "k must be in [1, %d]", kCandCap / 2);
+  Guard g(h);
+  int rc = set_require(h, "cms_set_top_k", measure, side);
+  if (rc) return rc;
+  std::vector<int64_t> idx;
+  if ((rc = common_indices(h, side, ids, nq, idx))) return rc;
+  if (nq == 0) return CMS_OK;
+  DevBuf o_ids, o_sc, o_cnt;
+  const size_t cells = (size_t)nq * (size_t)k;
+  CMS_HIP(o_ids.ensure(sizeof(int64_t) * cells));
+  CMS_HIP(o_sc.ensure(sizeof(double) * cells));
+  CMS_HIP(o_cnt.ensure(sizeof(int32_t) * (size_t)nq));
+  CMS_HIP(hipMemsetAsync(o_ids.ptr, 0xFF, sizeof(int64_t) * cells, h->stream));  // padding: ID -1, all-ones NaN
+  CMS_HIP(hipMemsetAsync(o_sc.ptr, 0xFF, sizeof(double) * cells, h->stream));
+  CMS_HIP(hipMemsetAsync(o_cnt.ptr, 0, sizeof(int32_t) * (size_t)nq, h->stream));
+  if ((rc = set_top_k(h, measure, side, idx.data(), nq, k, o_ids.as<int64_t>(), o_sc.as<double>(), o_cnt.as<int32_t>())))
     return rc;
   CMS_HIP(hipMemcpyAsync(out_ids, o_ids.ptr, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, h->stream));
   if (out_scores) CMS_HIP(hipMemcpyAsync(out_scores, o_sc.ptr, sizeof(double) * cells, hipMemcpyDeviceToHost, h->stream));

@@ -43,33 +43,6 @@ constexpr int kCommonThreads = 512;  // 8 waves; two workgroups per CU at the de
 constexpr int kCommonPairThreads = 256;
 constexpr int64_t kCommonChunkMax = 16384;  // queries per slab chunk (the tile grid is chunk x tiles)
 
-// One face of the model: n lists of (cross index ascending, unit, float), and
-// per cross index the lists that hold it (list index ascending, unit).
-struct CommonSide {
-  const int64_t* off;     // [n + 1]
-  const int32_t* key;     // the lists' cross indices
-  const int32_t* unit;
-  const float* val;
-  const int64_t* xoff;    // the cross lists
-  const int32_t* xlist;
-  const int32_t* xunit;
-  const uint64_t* U;      // [n] saturating sum of squared units
-  int64_t n;              // lists: the candidates, and the slab's columns
-  int64_t num;            // normalizeWeightResult's num: the other face's count
-  int32_t shift, weighted;
-};
-
-static CommonSide common_side(const cms_handle* h, int32_t side) {
-  const ExactModel& m = *h->exact;
-  if (side == CMS_SIDE_OWNER)
-    return CommonSide{m.off.as<int64_t>(),  m.item.as<int32_t>(), m.unit.as<int32_t>(),  m.val.as<float>(),
-                      m.ioff.as<int64_t>(), m.irow.as<int32_t>(), m.iunit.as<int32_t>(), m.U.as<uint64_t>(),
-                      m.n,                  m.nitems,             m.shift,               (int32_t)h->p.weighting};
-  return CommonSide{m.ioff.as<int64_t>(), m.irow.as<int32_t>(), m.iunit.as<int32_t>(), m.ival.as<float>(),
-                    m.off.as<int64_t>(),  m.item.as<int32_t>(), m.unit.as<int32_t>(),  m.iU.as<uint64_t>(),
-                    m.nitems,             m.n,                  m.shift,               (int32_t)h->p.weighting};
-}
-
 // ---- the tile kernel ----
 // block b: candidate tile b % ntiles of query b / ntiles (qidx: its list index)
 template <int MEASURE>
@@ -137,20 +110,7 @@ __global__ __launch_bounds__(kCommonThreads) void k_common_tile(CommonSide v, co
 }
 
 // ---- the pair kernel ----
-// elementwise: out[t] = similarity(i1[t], i2[t]), t < n1.
-// cross: query i (sel[i'] when sel is given, i' < n1) against column j < n2
-// (list i2[j]; i2 null: list j) into out[i * ld + j], or, scattered, into
-// out[i * ld + i2[j]] (the slab's column of that list).
-struct CommonPairArgs {
-  const int64_t* i1;
-  const int64_t* i2;
-  const int64_t* sel;
-  int64_t n1, n2;
-  int32_t cross, scatter;
-  double* out;
-  int64_t ld;
-};
-
+// (CommonPairArgs, cms_exact_model.h: elementwise, or cross with optional scatter)
 template <int MEASURE>
 __global__ __launch_bounds__(kCommonPairThreads) void k_common_pairs(CommonSide v, CommonPairArgs g) {
   const int64_t total = g.cross ? g.n1 * g.n2 : g.n1;

@@ -1,6 +1,8 @@
 // cms_exact_model.h -- the attached DataModel of a handle (exact_attach,
 // cms_exact.hip), as the files that score over it see it: cms_exact.hip (the
-// full-norm cosine) and cms_common.hip (the co-rated similarities).
+// full-norm cosine), cms_common.hip (the co-rated similarities) and
+// cms_set.hip (the set similarities), with the one view of a model's face
+// (CommonSide) and the pair kernels' argument that the last two share.
 #pragma once
 #include <vector>
 
@@ -43,5 +45,47 @@ template <class T>
 inline int upload(cms_handle* h, DevBuf& b, const std::vector<T>& v) {
   return upload(h, b, v.data(), v.size());
 }
+
+// One face of the model: n lists of (cross index ascending, unit, float), and
+// per cross index the lists that hold it (list index ascending, unit).
+struct CommonSide {
+  const int64_t* off;     // [n + 1]
+  const int32_t* key;     // the lists' cross indices
+  const int32_t* unit;
+  const float* val;
+  const int64_t* xoff;    // the cross lists
+  const int32_t* xlist;
+  const int32_t* xunit;
+  const uint64_t* U;      // [n] saturating sum of squared units
+  int64_t n;              // lists: the candidates, and the slab's columns
+  int64_t num;            // normalizeWeightResult's num: the other face's count
+  int32_t shift, weighted;
+};
+
+inline CommonSide common_side(const cms_handle* h, int32_t side) {
+  const ExactModel& m = *h->exact;
+  if (side == CMS_SIDE_OWNER)
+    return CommonSide{m.off.as<int64_t>(),  m.item.as<int32_t>(), m.unit.as<int32_t>(),  m.val.as<float>(),
+                      m.ioff.as<int64_t>(), m.irow.as<int32_t>(), m.iunit.as<int32_t>(), m.U.as<uint64_t>(),
+                      m.n,                  m.nitems,             m.shift,               (int32_t)h->p.weighting};
+  return CommonSide{m.ioff.as<int64_t>(), m.irow.as<int32_t>(), m.iunit.as<int32_t>(), m.ival.as<float>(),
+                    m.off.as<int64_t>(),  m.item.as<int32_t>(), m.unit.as<int32_t>(),  m.iU.as<uint64_t>(),
+                    m.nitems,             m.n,                  m.shift,               (int32_t)h->p.weighting};
+}
+
+// The pair kernels' argument (k_common_pairs, k_set_pairs).
+// elementwise: out[t] = similarity(i1[t], i2[t]), t < n1.
+// cross: query i (sel[i'] when sel is given, i' < n1) against column j < n2
+// (list i2[j]; i2 null: list j) into out[i * ld + j], or, scattered, into
+// out[i * ld + i2[j]] (the slab's column of that list).
+struct CommonPairArgs {
+  const int64_t* i1;
+  const int64_t* i2;
+  const int64_t* sel;
+  int64_t n1, n2;
+  int32_t cross, scatter;
+  double* out;
+  int64_t ld;
+};
 
 }  // namespace cms

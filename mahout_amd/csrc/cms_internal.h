@@ -232,6 +232,7 @@ struct Tunables {
   int exact_tile = 0;       // CMS_EXACT_TILE: candidate rows per workgroup of k_exact_tile, a multiple of 64 (0: kExactTile)
   int exact_est_tile = 0;   // CMS_EXACT_EST_TILE: candidate slots per workgroup of k_exact_estimate, a multiple of 64 (0: kExactEstTile)
   int common_tile = 0;      // CMS_COMMON_TILE: candidates per workgroup of k_common_tile, a multiple of 64 (0: the measure's default)
+  int set_tile = 0;         // CMS_SET_TILE: candidates per workgroup of k_set_tile, a multiple of 64 (0: kSetTileDefault)
 };
 struct ExactModel;  // the attached DataModel of the exact cosine (cms_exact.hip)
 }  // namespace cms
@@ -755,6 +756,13 @@ int common_pair_call(cms_handle* h, int32_t measure, int32_t side, const int64_t
 // top_k_rows'; the IDs are owner IDs or item keys
 int common_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* idx, int64_t nq, int32_t k,
                  int64_t* d_ids, double* d_scores, int32_t* d_counts);
+// ---- cms_set.hip: the set similarities over the attached DataModel ----
+// (h->exact is non-null; measure and side are validated by the caller: CMS_SET_*, CMS_SIDE_*; indices as
+// common_pair_call's and common_top_k's)
+int set_pair_call(cms_handle* h, int32_t measure, int32_t side, const int64_t* i1, int64_t n1, const int64_t* i2,
+                  int64_t n2, bool cross, double* out);
+int set_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* idx, int64_t nq, int32_t k, int64_t* d_ids,
+              double* d_scores, int32_t* d_counts);
 // ---- cms_f64.hip (CMS_COUNTER_F64) ----
 int f64_ingest_csr(cms_handle* h, const int64_t* d_off, const int64_t* d_key, const float* d_val);
 int f64_ingest_coo_host(cms_handle* h, const int64_t* owner, const int64_t* key, const float* val, int64_t np);

@@ -509,6 +509,58 @@ class SketchTable:
         check(self._lib.cms_common_top_k(self._h, ms, sd, _ptr(ids), ids.size, int(k), _ptr(out), _ptr(sc), _ptr(cnt)))
         return out, sc, cnt
 
+    # -- the set similarities over the attached DataModel --
+    SET_MEASURES = {"cooccurrence": 0, "tanimoto": 1, "city_block": 2, "loglikelihood": 3}  # CMS_SET_*
+
+    def attach_sets(self, offsets, keys=None):
+        """The owners' DataModel for the set similarities: a CSR over the
+        table's owner rows (keys strictly ascending within a row), or a
+        GenericDataModel with or without preference values.  The set measures
+        read no value, so every entry is attached with 1.0
+        (cms_exact_attach_csr); a second call replaces the model."""
+        if keys is None and hasattr(offsets, "offsets"):
+            offsets, keys = offsets.offsets, offsets.keys
+        keys = np.ascontiguousarray(keys, np.int64).reshape(-1)
+        self.attach_exact(offsets, keys, np.ones(keys.size, np.float32))
+
+    @classmethod
+    def _set_args(cls, measure, side):
+        return (int(cls.SET_MEASURES.get(measure, measure)), int(cls.COMMON_SIDES.get(side, side)))
+
+    def set_similarities(self, id1, ids2, measure="loglikelihood", side="owner"):
+        """userSimilarity (side="owner", owner IDs) or itemSimilarity
+        (side="key", the attached keys) of id1 with every ids2[t] under
+        measure: "cooccurrence", "tanimoto", "city_block" or "loglikelihood",
+        from the number of entries the two lists share and their lengths
+        (cms_set_similarities)."""
+        ids2 = np.ascontiguousarray(ids2, np.int64).reshape(-1)
+        out = np.zeros(ids2.size, np.float64)
+        ms, sd = self._set_args(measure, side)
+        check(self._lib.cms_set_similarities(self._h, ms, sd, int(id1), _ptr(ids2), ids2.size, _ptr(out)))
+        return out
+
+    def set_pairs(self, ids1, ids2, measure="loglikelihood", side="owner"):
+        """similarity(ids1[t], ids2[t]), element-wise (cms_set_pairs)."""
+        ids1 = np.ascontiguousarray(ids1, np.int64).reshape(-1)
+        ids2 = np.ascontiguousarray(ids2, np.int64).reshape(-1)
+        if ids1.size != ids2.size:
+            raise ValueError("ids1 and ids2 differ in length")
+        out = np.zeros(ids1.size, np.float64)
+        ms, sd = self._set_args(measure, side)
+        check(self._lib.cms_set_pairs(self._h, ms, sd, _ptr(ids1), _ptr(ids2), ids1.size, _ptr(out)))
+        return out
+
+    def set_top_k(self, ids, k, measure="loglikelihood", side="owner"):
+        """The k most similar owners (or keys) of each ID under measure
+        (cms_set_top_k), shaped and ordered as common_top_k."""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        out = np.zeros((ids.size, k), np.int64)
+        sc = np.zeros((ids.size, k), np.float64)
+        cnt = np.zeros(ids.size, np.int32)
+        ms, sd = self._set_args(measure, side)
+        check(self._lib.cms_set_top_k(self._h, ms, sd, _ptr(ids), ids.size, int(k), _ptr(out), _ptr(sc), _ptr(cnt)))
+        return out, sc, cnt
+
     # -- anonymous profiles: preferences that are no row of the table --
     @staticmethod
     def _profile(keys, vals):

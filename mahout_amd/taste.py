@@ -650,6 +650,71 @@ class EuclideanDistanceSimilarity(_CommonSimilarity):
     MEASURE = "euclidean"
 
 
+class _SetSimilarity(_CommonSimilarity):
+    """The reference's similarities for preference data without values, over the
+    DataModel on the GPU (cms_set_*): each is a function of the number of
+    entries two lists share, the two list lengths and, for log-likelihood,
+    getNumItems() (userSimilarity) or getNumUsers() (itemSimilarity).  A
+    DataModel with or without preference values is accepted and its values are
+    never read; no Weighting applies.  The object owns a minimal handle as
+    CosineSimilarity does; the methods, and what is not served, are
+    _CommonSimilarity's."""
+
+    def __init__(self, dataModel, device=-1):
+        self._model = dataModel
+        self._table = SketchTable(dataModel.getNumUsers(), depth=1, width=32, device=device,
+                                  owner_ids=dataModel.getUserIDs())
+        try:
+            self._table.attach_sets(dataModel)
+        except _lib.CmsError as e:
+            self._table.close()
+            raise _map_error(e)
+
+    def setPreferenceInferrer(self, inferrer):
+        raise NotImplementedError("setPreferenceInferrer: the reference's class throws UnsupportedOperationException")
+
+    def _similarities(self, side, kind, id1, ids2):
+        try:
+            return self._table.set_similarities(id1, ids2, self.MEASURE, side)
+        except _lib.CmsError as e:
+            raise _map_error(e, kind)
+
+    def _top(self, userIDs, k):
+        try:
+            return self._table.set_top_k(userIDs, k, self.MEASURE, "owner")
+        except _lib.CmsError as e:
+            raise _map_error(e, "user")
+
+    def estimatePreferences(self, theUserID, theNeighborhood, itemIDs, capper=None):
+        raise NotImplementedError("the boolean recommenders' estimates are not served on the device")
+
+    def recommendBatch(self, userIDs, nb_offsets, neighborIDs, modelCSR, howMany, includeKnownItems=False, capper=None):
+        raise NotImplementedError("the boolean recommenders' estimates are not served on the device")
+
+    def refresh(self, alreadyRefreshed=None):
+        try:
+            self._table.attach_sets(self._model)
+        except _lib.CmsError as e:
+            raise _map_error(e)
+
+
+class TanimotoCoefficientSimilarity(_SetSimilarity):
+    """TanimotoCoefficientSimilarity(DataModel) (T/impl/similarity/TanimotoCoefficientSimilarity.java)."""
+    MEASURE = "tanimoto"
+
+
+class LogLikelihoodSimilarity(_SetSimilarity):
+    """LogLikelihoodSimilarity(DataModel) (T/impl/similarity/LogLikelihoodSimilarity.java): the reference's
+    operations in the reference's order, to within the 1-ulp freedom of Math.log (cms_set.h)."""
+    MEASURE = "loglikelihood"
+
+
+class CityBlockSimilarity(_SetSimilarity):
+    """CityBlockSimilarity(DataModel) (T/impl/similarity/CityBlockSimilarity.java): never NaN, so a
+    neighbourhood of n users is always full."""
+    MEASURE = "city_block"
+
+
 class NearestNUserNeighborhood:
     """NearestNUserNeighborhood(n, similarity, model): the n most similar
     users (T/impl/neighborhood/NearestNUserNeighborhood.java) -- TopItems
