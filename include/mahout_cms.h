@@ -130,7 +130,10 @@ int cms_shape_from_delta_epsilon(double delta, double epsilon, int32_t* width, i
  *                         up to a multiple of 64 (default and most, by measure: 5440 Euclidean,
  *                         2304 uncentered cosine, 1472 Pearson -- just under 64 KiB of LDS cells)
  *   CMS_SET_TILE=<n>      candidates per workgroup of the set similarities' tile kernel, rounded up
- *                         to a multiple of 64 (default and most: 16384, 64 KiB of LDS counts) */
+ *                         to a multiple of 64 (default and most: 16384, 64 KiB of LDS counts)
+ *   CMS_SET_EST_TILE=<n>  items per workgroup of the set similarities' item-based estimate kernel,
+ *                         rounded up to a multiple of 64 (default and most: 4096 boolean, 2688
+ *                         weighted -- 64 KiB and 64,512 B of LDS cells) */
 int cms_create(const cms_params* p, cms_handle** out);
 void cms_destroy(cms_handle* h);
 const char* cms_last_error(void);
@@ -946,6 +949,51 @@ int cms_set_pairs(cms_handle* h, int32_t measure, int32_t side, const int64_t* i
  * cms_common_top_k.  Timing scopes "set_tile", "top_k". */
 int cms_set_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* ids, int64_t nq, int32_t k,
                   int64_t* out_ids, double* out_scores, int32_t* out_counts);
+
+/* ---- item-based recommenders over the set similarities ----------------------
+ * The estimates of the reference's item-based recommenders with one of the set
+ * similarities as ItemSimilarity, over the attached model's key side (its
+ * items; the model's rows are the users):
+ *   CMS_ITEM_EST_WEIGHTED  GenericItemBasedRecommender.doEstimatePreference
+ *     (:231-259): over sim = itemSimilarity(candidate, preferred item), NaN
+ *     skipped, preference += sim * pref and totalSimilarity += sim in
+ *     preference order; fewer than two data points give NaN; (float)(preference
+ *     / totalSimilarity), then the capper when use_capper;
+ *   CMS_ITEM_EST_BOOLEAN   GenericBooleanPrefItemBasedRecommender
+ *     .doEstimatePreference (:52-64): (float) of the sum of the similarities
+ *     that are not NaN, NaN when there is none.  No capper, no preference value:
+ *     pref_vals may be NULL, use_capper and the caps are not read.
+ * Every candidate's fp64 sums grow in preference order, one correctly rounded
+ * operation per data point, so with co-occurrence, Tanimoto and city block an
+ * estimate has the reference's bits; with log-likelihood it is that sum over
+ * the values cms_set_similarities returns.
+ *
+ * cms_set_item_estimates_batch is laid out and validated as
+ * cms_item_estimates_batch: user u's preferred items pref_items / pref_vals
+ * [pref_offsets[u], pref_offsets[u + 1]) in PreferenceArray order, its
+ * candidates cand_items [cand_offsets[u], cand_offsets[u + 1]) (any order,
+ * repeats allowed), one float per candidate into out.  CMS_E_STATE without a
+ * model, CMS_E_PARAM for an unknown measure or kind, CMS_E_NO_SUCH_ID for a
+ * preferred item the model lacks, before anything is written; a candidate the
+ * model lacks reads NaN.  Timing scope "set_item_estimate". */
+#define CMS_ITEM_EST_WEIGHTED 0
+#define CMS_ITEM_EST_BOOLEAN 1
+int cms_set_item_estimates_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* pref_offsets,
+                                 const int64_t* pref_items, const float* pref_vals, const int64_t* cand_offsets,
+                                 const int64_t* cand_items, int32_t use_capper, float cap_min, float cap_max,
+                                 float* out);
+/* recommend(userID, howMany) of those recommenders for every user of user_ids
+ * (owner IDs): the attached model is the DataModel, as in
+ * cms_exact_recommend_batch -- its rows give the preferences (for
+ * CMS_ITEM_EST_WEIGHTED the values it was attached with) and the candidates of
+ * strategy 0 (PreferredItemsNeighborhoodCandidateItemsStrategy) or 1
+ * (AllUnknownItemsCandidateItemsStrategy) in FastIDSet order; one estimate
+ * batch, then TopItems.getTopItems.  A user without preferences is recommended
+ * nothing.  Outputs as cms_item_recommend_batch's. */
+int cms_set_item_recommend_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* user_ids,
+                                 int32_t strategy, int32_t how_many, int32_t include_known, int32_t use_capper,
+                                 float cap_min, float cap_max, int32_t* out_counts, int64_t* out_items,
+                                 float* out_values);
 
 /* ---- instrumentation ------------------------------------------------------- */
 typedef struct cms_stats {

@@ -362,6 +362,7 @@ static int create_impl(const cms_params* p, bool per_owner, cms_handle** out) {
     h->tune.exact_est_tile = std::max(0, num("CMS_EXACT_EST_TILE", 0));
     h->tune.common_tile = std::max(0, num("CMS_COMMON_TILE", 0));
     h->tune.set_tile = std::max(0, num("CMS_SET_TILE", 0));
+    h->tune.set_est_tile = std::max(0, num("CMS_SET_EST_TILE", 0));
   }
   h->per_owner = per_owner;
   h->f64 = f64;
@@ -1986,6 +1987,92 @@ int cms_set_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* i
   if (out_scores) CMS_HIP(hipMemcpyAsync(out_scores, o_sc.ptr, sizeof(double) * cells, hipMemcpyDeviceToHost, h->stream));
   CMS_HIP(hipMemcpyAsync(out_counts, o_cnt.ptr, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
   CMS_HIP(hipStreamSynchronize(h->stream));
+  return CMS_OK;
+}
+
+// ---- the item-based recommenders over the set similarities (cms_set_item.hip) ----
+
+static int set_item_require(cms_handle* h, const char* what, int32_t measure, int32_t kind) {
+  if (kind != CMS_ITEM_EST_WEIGHTED && kind != CMS_ITEM_EST_BOOLEAN)
+    return set_error(CMS_E_PARAM, "%s: unknown kind %d", what, (int)kind);
+  return set_require(h, what, measure, CMS_SIDE_KEY);
+}
+
+int cms_set_item_estimates_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* pref_offsets,
+                                 const int64_t* pref_items, const float* pref_vals, const int64_t* cand_offsets,
+                                 const int64_t* cand_items, int32_t use_capper, float cap_min, float cap_max,
+                                 float* out) {
+  if (!h || n < 0 || (n > 0 && (!pref_offsets || !cand_offsets))) return set_error(CMS_E_PARAM, "null argument");
+  Guard g(h);
+  int rc = set_item_require(h, "cms_set_item_estimates_batch", measure, kind);
+  if (rc) return rc;
+  if (n == 0) return CMS_OK;
+  if ((rc = check_offsets("pref_offsets", pref_offsets, n)) || (rc = check_offsets("cand_offsets", cand_offsets, n)))
+    return rc;
+  const int64_t M = pref_offsets[n], Q = cand_offsets[n];
+  if ((M > 0 && (!pref_items || (kind == CMS_ITEM_EST_WEIGHTED && !pref_vals))) || (Q > 0 && (!cand_items || !out)))
+    return set_error(CMS_E_PARAM, "null argument");
+  if (Q >= (int64_t(1) << 31)) return set_error(CMS_E_PARAM, "too many candidate items in one batch");
+  return set_item_estimate_batch(h, measure, kind, n, pref_offsets, pref_items, pref_vals, cand_offsets, cand_items,
+                                 use_capper, cap_min, cap_max, out);
+}
+
+int cms_set_item_recommend_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* user_ids,
+                                 int32_t strategy, int32_t how_many, int32_t include_known, int32_t use_capper,
+                                 float cap_min, float cap_max, int32_t* out_counts, int64_t* out_items,
+                                 float* out_values) {
+  if (!h || n < 0 || (n > 0 && (!user_ids || !out_counts || !out_items || !out_values)))
+    return set_error(CMS_E_PARAM, "null argument");
+  if (how_many < 1) return set_error(CMS_E_PARAM, "howMany must be at least 1");
+  if (strategy != 0 && strategy != 1)
+    return set_error(CMS_E_PARAM, "strategy must be 0 (preferred items' neighbourhood) or 1 (all unknown items)");
+  Guard g(h);
+  int rc = set_item_require(h, "cms_set_item_recommend_batch", measure, kind);
+  if (rc) return rc;
+  if (n == 0) return CMS_OK;
+  // the attached model is the DataModel: owner rows are its rows
+  std::vector<int64_t> urow((size_t)n);
+  for (int64_t u = 0; u < n; ++u)
+    if ((rc = row_of(h, user_ids[u], &urow[(size_t)u]))) return rc;
+  const int64_t *pref_offsets, *pref_items;
+  exact_host_csr(h, &pref_offsets, &pref_items);
+  const float* pref_vals = nullptr;  // read by the weighted kind alone
+  if (kind == CMS_ITEM_EST_WEIGHTED && (rc = exact_host_vals(h, &pref_vals))) return rc;
+  // candidates per user (host threads), in FastIDSet iteration order
+  ItemCandidates model(h->n, pref_offsets, pref_items);
+  std::vector<std::vector<int64_t>> cand((size_t)n);
+  const int threads = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
+  parallel_users(n, threads, [&](int64_t u) {
+    const int64_t r = urow[(size_t)u], m = pref_offsets[r + 1] - pref_offsets[r];
+    if (m == 0) return;  // recommend(): a user without preferences is recommended nothing
+    model.candidates(pref_items + pref_offsets[r], m, strategy, include_known != 0, cand[(size_t)u]);
+  });
+  // the users' preferences and candidates as one batch
+  std::vector<int64_t> p_off((size_t)n + 1, 0), c_off((size_t)n + 1, 0);
+  for (int64_t u = 0; u < n; ++u) {
+    const int64_t r = urow[(size_t)u];
+    p_off[(size_t)u + 1] = p_off[(size_t)u] + (pref_offsets[r + 1] - pref_offsets[r]);
+    c_off[(size_t)u + 1] = c_off[(size_t)u] + (int64_t)cand[(size_t)u].size();
+  }
+  if (c_off[(size_t)n] >= (int64_t(1) << 31)) return set_error(CMS_E_PARAM, "too many candidate items in one batch");
+  std::vector<int64_t> p_items((size_t)p_off[(size_t)n]), c_items((size_t)c_off[(size_t)n]);
+  std::vector<float> p_vals(pref_vals ? p_items.size() : 0);
+  for (int64_t u = 0; u < n; ++u) {
+    const int64_t r = urow[(size_t)u];
+    std::copy(pref_items + pref_offsets[r], pref_items + pref_offsets[r + 1], p_items.begin() + p_off[(size_t)u]);
+    if (pref_vals)
+      std::copy(pref_vals + pref_offsets[r], pref_vals + pref_offsets[r + 1], p_vals.begin() + p_off[(size_t)u]);
+    std::copy(cand[(size_t)u].begin(), cand[(size_t)u].end(), c_items.begin() + c_off[(size_t)u]);
+  }
+  std::vector<float> est(c_items.size());
+  if ((rc = set_item_estimate_batch(h, measure, kind, n, p_off.data(), p_items.data(), p_vals.data(), c_off.data(),
+                                    c_items.data(), use_capper, cap_min, cap_max, est.data())))
+    return rc;
+  parallel_users(n, threads, [&](int64_t u) {
+    const int64_t o = c_off[(size_t)u];
+    out_counts[u] = recommend_top_items(how_many, c_items.data() + o, est.data() + o, c_off[(size_t)u + 1] - o,
+                                        out_items + u * (int64_t)how_many, out_values + u * (int64_t)how_many);
+  });
   return CMS_OK;
 }
 

@@ -429,6 +429,18 @@ void exact_host_csr(const cms_handle* h, const int64_t** off, const int64_t** ke
   *keys = h->exact->h_keys.data();
 }
 
+int exact_host_vals(cms_handle* h, const float** vals) {
+  ExactModel& m = *h->exact;
+  if (m.h_vals.size() != (size_t)m.npairs) {  // kept from here on: an attach that never asks pays nothing
+    std::vector<float> v((size_t)m.npairs);
+    CMS_HIP(hipMemcpyAsync(v.data(), m.val.ptr, sizeof(float) * v.size(), hipMemcpyDeviceToHost, h->stream));
+    CMS_HIP(hipStreamSynchronize(h->stream));
+    m.h_vals.swap(v);
+  }
+  *vals = m.h_vals.data();
+  return CMS_OK;
+}
+
 int exact_estimate_batch(cms_handle* h, int64_t n, const int64_t* user_rows, const int64_t* nb_offsets,
                          const int64_t* nb_rows, const int64_t* item_offsets, const int64_t* item_keys,
                          int32_t use_capper, float cap_min, float cap_max, float* out) {

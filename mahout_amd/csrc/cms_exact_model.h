@@ -17,6 +17,7 @@ struct ExactModel {
   std::vector<uint8_t> h_seq;  // [n] 1: not integer-eligible
   std::vector<int64_t> ids;    // [nitems] getItemIDs(): the keys, sorted and unique (key -> dense item index)
   std::vector<int64_t> h_off, h_keys;  // the attached CSR's offsets and keys: the DataModel of the recommend call
+  std::vector<float> h_vals;           // ... and its values, copied back from val by the first call that reads them (exact_host_vals)
   int64_t n_seq = 0;
   DevBuf off, item, val, unit;  // owner side: [n + 1] i64, [np] dense item (i32), float, unit (i32)
   DevBuf ioff, irow, iunit;     // item side: [nitems + 1] i64, [np] owner row ascending (i32), unit (i32)
@@ -24,6 +25,7 @@ struct ExactModel {
   DevBuf seq_rows;              // [n_seq] the non-eligible rows (i64)
   DevBuf q1, q2, sel, out;      // a call's rows, selected queries and results
   DevBuf e_urow, e_nboff, e_slot, e_tiles, e_est;  // an estimate batch: users' rows, neighbour offsets, plan, estimates
+  DevBuf i_poff, i_pidx, i_pval;  // an item-based estimate batch (cms_set_item.hip): preference offsets, dense items, values
   // the co-rated similarities (cms_common.hip): the floats in posting-list
   // order, the items' U over their posting lists, the item keys on the device
   // (the top-k's IDs on the key side), and per side the lists that are not

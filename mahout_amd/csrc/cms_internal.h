@@ -233,6 +233,7 @@ struct Tunables {
   int exact_est_tile = 0;   // CMS_EXACT_EST_TILE: candidate slots per workgroup of k_exact_estimate, a multiple of 64 (0: kExactEstTile)
   int common_tile = 0;      // CMS_COMMON_TILE: candidates per workgroup of k_common_tile, a multiple of 64 (0: the measure's default)
   int set_tile = 0;         // CMS_SET_TILE: candidates per workgroup of k_set_tile, a multiple of 64 (0: kSetTileDefault)
+  int set_est_tile = 0;     // CMS_SET_EST_TILE: items per workgroup of k_set_item_estimate, a multiple of 64 (0: the kind's default)
 };
 struct ExactModel;  // the attached DataModel of the exact cosine (cms_exact.hip)
 }  // namespace cms
@@ -745,6 +746,8 @@ int exact_estimate_batch(cms_handle* h, int64_t n, const int64_t* user_rows, con
                          int32_t use_capper, float cap_min, float cap_max, float* out);
 // the attached CSR's offsets [n + 1] and keys, as the host gave them (they live as long as the model)
 void exact_host_csr(const cms_handle* h, const int64_t** off, const int64_t** keys);
+// ... and its preference values, in the keys' order: copied back from the device by the first call, then kept
+int exact_host_vals(cms_handle* h, const float** vals);
 // ---- cms_common.hip: the co-rated similarities over the attached DataModel ----
 // (h->exact is non-null; measure and side are validated by the caller: CMS_SIM_*, CMS_SIDE_*)
 // the index of an ID on a side: the owner row is the caller's; here the dense item index of a key
@@ -763,6 +766,16 @@ int set_pair_call(cms_handle* h, int32_t measure, int32_t side, const int64_t* i
                   int64_t n2, bool cross, double* out);
 int set_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* idx, int64_t nq, int32_t k, int64_t* d_ids,
               double* d_scores, int32_t* d_counts);
+// ---- cms_set_item.hip: the item-based recommenders' estimates over the set similarities ----
+// (h->exact is non-null; measure and kind are validated by the caller: CMS_SET_*, CMS_ITEM_EST_*)
+// doEstimatePreference of GenericItemBasedRecommender (weighted) or GenericBooleanPrefItemBasedRecommender
+// (boolean) for a batch of users: user u's preferred item keys pref_keys / pref_vals [pref_offsets[u] ..
+// pref_offsets[u + 1]) in preference order (pref_vals is not read for boolean) and candidate keys cand_keys
+// [cand_offsets[u] .. cand_offsets[u + 1]); one float per candidate.  Host arrays in, host estimates out
+// (blocking); the offsets are validated by the caller.  A preferred key the model lacks: CMS_E_NO_SUCH_ID.
+int set_item_estimate_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* pref_offsets,
+                            const int64_t* pref_keys, const float* pref_vals, const int64_t* cand_offsets,
+                            const int64_t* cand_keys, int32_t use_capper, float cap_min, float cap_max, float* out);
 // ---- cms_f64.hip (CMS_COUNTER_F64) ----
 int f64_ingest_csr(cms_handle* h, const int64_t* d_off, const int64_t* d_key, const float* d_val);
 int f64_ingest_coo_host(cms_handle* h, const int64_t* owner, const int64_t* key, const float* val, int64_t np);

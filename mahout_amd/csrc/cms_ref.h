@@ -220,6 +220,24 @@ struct ItemEstimate {
   }
 };
 
+// GenericBooleanPrefItemBasedRecommender.doEstimatePreference (:52-64) for one
+// candidate item: totalSimilarity += sim (fp64, one rounded addition) for every
+// similarity that is not NaN, in preference order; (float) totalSimilarity
+// when there was one, else NaN.  No count rule, no capper, no preference value.
+struct BoolItemEstimate {
+  double total = 0.0;
+  int found = 0;
+  CMS_HD void add(const double* sims, int64_t m) {
+    for (int64_t i = 0; i < m; ++i) {
+      const double s = sims[i];
+      if (s != s) continue;
+      found = 1;
+      total = __dadd_rn(total, s);
+    }
+  }
+  CMS_HD float finish() const { return found ? (float)total : __builtin_nanf(""); }
+};
+
 CMS_HD float item_estimate_one(const double* sims, const float* prefs, int64_t m, int use_capper, float lo, float hi) {
   ItemEstimate e;
   e.add(sims, prefs, m);

@@ -512,16 +512,18 @@ class SketchTable:
     # -- the set similarities over the attached DataModel --
     SET_MEASURES = {"cooccurrence": 0, "tanimoto": 1, "city_block": 2, "loglikelihood": 3}  # CMS_SET_*
 
-    def attach_sets(self, offsets, keys=None):
+    def attach_sets(self, offsets, keys=None, vals=None):
         """The owners' DataModel for the set similarities: a CSR over the
         table's owner rows (keys strictly ascending within a row), or a
         GenericDataModel with or without preference values.  The set measures
         read no value, so every entry is attached with 1.0
-        (cms_exact_attach_csr); a second call replaces the model."""
+        (cms_exact_attach_csr) unless vals gives the preferences' values, which
+        only the weighted item-based estimate reads (set_item_recommend_batch);
+        a second call replaces the model."""
         if keys is None and hasattr(offsets, "offsets"):
             offsets, keys = offsets.offsets, offsets.keys
         keys = np.ascontiguousarray(keys, np.int64).reshape(-1)
-        self.attach_exact(offsets, keys, np.ones(keys.size, np.float32))
+        self.attach_exact(offsets, keys, np.ones(keys.size, np.float32) if vals is None else vals)
 
     @classmethod
     def _set_args(cls, measure, side):
@@ -560,6 +562,51 @@ class SketchTable:
         ms, sd = self._set_args(measure, side)
         check(self._lib.cms_set_top_k(self._h, ms, sd, _ptr(ids), ids.size, int(k), _ptr(out), _ptr(sc), _ptr(cnt)))
         return out, sc, cnt
+
+    # -- item-based recommenders over the set similarities --
+    ITEM_EST_KINDS = {"weighted": 0, "boolean": 1}  # CMS_ITEM_EST_*
+
+    def set_item_estimates_batch(self, pref_offsets, pref_items, pref_vals, cand_offsets, cand_items,
+                                 measure="loglikelihood", kind="boolean", capper=None):
+        """cms_set_item_estimates_batch: doEstimatePreference of
+        GenericItemBasedRecommender (kind="weighted") or
+        GenericBooleanPrefItemBasedRecommender (kind="boolean") with a set
+        similarity over the attached model's items, shaped as
+        item_estimates_batch; pref_vals may be None for "boolean".  One float32
+        per candidate; a candidate the model lacks reads NaN."""
+        pi = np.ascontiguousarray(pref_items, np.int64).reshape(-1)
+        pv = None if pref_vals is None else np.ascontiguousarray(pref_vals, np.float32).reshape(-1)
+        ci = np.ascontiguousarray(cand_items, np.int64).reshape(-1)
+        n = np.asarray(pref_offsets).size - 1
+        po = self._csr("pref_offsets", pref_offsets, n, pi, *(() if pv is None else (pv,)))
+        co = self._csr("cand_offsets", cand_offsets, n, ci)
+        out = np.zeros(ci.size, np.float32)
+        lo, hi = capper if capper is not None else (0.0, 0.0)
+        ms, _ = self._set_args(measure, "key")
+        check(self._lib.cms_set_item_estimates_batch(self._h, ms, int(self.ITEM_EST_KINDS.get(kind, kind)), n, _ptr(po),
+                                                     _ptr(pi), _ptr(pv), _ptr(co), _ptr(ci), int(capper is not None),
+                                                     float(lo), float(hi), _ptr(out)))
+        return out
+
+    def set_item_recommend_batch(self, user_ids, how_many, measure="loglikelihood", kind="boolean",
+                                 strategy="preferred", include_known=False, capper=None):
+        """cms_set_item_recommend_batch: recommend() of those recommenders for
+        every user of user_ids, the attached model as the DataModel (kind
+        "weighted" reads the values it was attached with).  Returns (counts
+        [n], items [n][how_many], values [n][how_many] float32)."""
+        us = np.ascontiguousarray(user_ids, np.int64).reshape(-1)
+        if how_many < 1:
+            raise ValueError("howMany must be at least 1")
+        counts = np.zeros(us.size, np.int32)
+        items = np.full((us.size, how_many), -1, np.int64)
+        vals = np.full((us.size, how_many), np.nan, np.float32)
+        lo, hi = capper if capper is not None else (0.0, 0.0)
+        ms, _ = self._set_args(measure, "key")
+        check(self._lib.cms_set_item_recommend_batch(self._h, ms, int(self.ITEM_EST_KINDS.get(kind, kind)), us.size,
+                                                     _ptr(us), int(self.ITEM_STRATEGIES.get(strategy, strategy)),
+                                                     int(how_many), int(bool(include_known)), int(capper is not None),
+                                                     float(lo), float(hi), _ptr(counts), _ptr(items), _ptr(vals)))
+        return counts, items, vals
 
     # -- anonymous profiles: preferences that are no row of the table --
     @staticmethod

@@ -665,10 +665,16 @@ class _SetSimilarity(_CommonSimilarity):
         self._table = SketchTable(dataModel.getNumUsers(), depth=1, width=32, device=device,
                                   owner_ids=dataModel.getUserIDs())
         try:
-            self._table.attach_sets(dataModel)
+            self._attach()
         except _lib.CmsError as e:
             self._table.close()
             raise _map_error(e)
+
+    def _attach(self):
+        """The model's lists, with its values when it has them: no measure reads them, the weighted
+        item-based estimate of itemRecommendBatch does."""
+        m = self._model
+        self._table.attach_sets(m, vals=getattr(m, "values", None) if m.hasPreferenceValues() else None)
 
     def setPreferenceInferrer(self, inferrer):
         raise NotImplementedError("setPreferenceInferrer: the reference's class throws UnsupportedOperationException")
@@ -691,9 +697,24 @@ class _SetSimilarity(_CommonSimilarity):
     def recommendBatch(self, userIDs, nb_offsets, neighborIDs, modelCSR, howMany, includeKnownItems=False, capper=None):
         raise NotImplementedError("the boolean recommenders' estimates are not served on the device")
 
+    # the item-based recommenders' device route (GenericItemBasedRecommender looks for these three)
+    def servesItemModel(self, dataModel):
+        """Whether the attached model is dataModel: its rows are then the recommender's users."""
+        return dataModel is self._model
+
+    def itemEstimatesBatch(self, pref_offsets, pref_items, pref_vals, cand_offsets, cand_items, kind, capper=None):
+        """doEstimatePreference for many users in one device batch (cms_set_item_estimates_batch)."""
+        return self._table.set_item_estimates_batch(pref_offsets, pref_items, pref_vals, cand_offsets, cand_items,
+                                                    self.MEASURE, kind, capper)
+
+    def itemRecommendBatch(self, userIDs, howMany, kind, strategy, includeKnownItems=False, capper=None):
+        """recommend for many users (cms_set_item_recommend_batch): (counts, items, values)."""
+        return self._table.set_item_recommend_batch(userIDs, howMany, self.MEASURE, kind, strategy, includeKnownItems,
+                                                    capper)
+
     def refresh(self, alreadyRefreshed=None):
         try:
-            self._table.attach_sets(self._model)
+            self._attach()
         except _lib.CmsError as e:
             raise _map_error(e)
 
@@ -927,6 +948,21 @@ def item_estimate(sims, prefs, capper=None):
     return e
 
 
+def bool_item_estimate(sims):
+    """GenericBooleanPrefItemBasedRecommender.doEstimatePreference (:52-64)
+    restated: totalSimilarity += sim in order (fp64) for every similarity that
+    is not NaN; (float) totalSimilarity when there was one, else NaN.  np.float32."""
+    total = np.float64(0.0)
+    found = False
+    for s in np.asarray(sims, np.float64).tolist():
+        if s != s:
+            continue
+        found = True
+        total = total + np.float64(s)
+    with np.errstate(over="ignore"):
+        return np.float32(total) if found else np.float32(np.nan)
+
+
 class FullRunningAverage:
     """T/impl/common/FullRunningAverage.java:30-55: NaN until the first datum,
     then average * (count - 1) / count + datum / count."""
@@ -1042,7 +1078,17 @@ class GenericItemBasedRecommender:
     (SketchTable.item_recommend_batch / item_estimates_batch /
     similarity_block).  Any other ItemSimilarity, and a CosineCM whose table
     those calls refuse (per-owner shapes, fp64 counters), is served through
-    itemSimilarities per candidate and item_estimate on the host."""
+    itemSimilarities per candidate and item_estimate on the host.  A similarity
+    that offers itemEstimatesBatch / itemRecommendBatch over this very
+    dataModel (the set similarities: Tanimoto, log-likelihood, city block) puts
+    the estimates of a call, and with a built-in strategy the whole
+    recommend_all, into one device batch (cms_set_item_*).  That recommend_all
+    reads the preferences, and the weighted kind their values, from the model
+    as the similarity attached it, while doEstimatePreferences and the host
+    route read dataModel itself: after a change of the model, refresh() the
+    similarity, or the two can disagree (as with CosineSimilarity's batch)."""
+
+    KIND = "weighted"  # CMS_ITEM_EST_*: which doEstimatePreference the device batch runs
 
     def __init__(self, dataModel, similarity, candidateItemsStrategy=None, mostSimilarItemsCandidateItemsStrategy=None):
         if similarity is None:
@@ -1063,6 +1109,17 @@ class GenericItemBasedRecommender:
         if isinstance(s, CosineCM) and not s._per_owner and s.table.counters == "u32":
             return s.table
         return None
+
+    def _batch_sim(self):
+        """The similarity when it serves the item-based device batch over this recommender's own model, else None:
+        the capability is asked for, not a type."""
+        s = self._sim
+        if all(callable(getattr(s, a, None)) for a in ("servesItemModel", "itemEstimatesBatch", "itemRecommendBatch")):
+            return s if s.servesItemModel(self._model) else None
+        return None
+
+    def _host_estimate(self, sims, vals):
+        return item_estimate(sims, vals, self._capper)
 
     def _model_csr(self):
         """(user IDs ascending, offsets, item IDs, float values) in getPreferencesFromUser order, built once."""
@@ -1097,7 +1154,13 @@ class GenericItemBasedRecommender:
                 return t.item_estimates_batch([0, keys.size], keys, vals, [0, items.size], items, self._capper)
             except _lib.CmsError as e:
                 raise _map_error(e, "item")
-        return np.array([item_estimate(self._sim.itemSimilarities(int(i), keys), vals, self._capper)
+        b = self._batch_sim()
+        if b is not None:
+            try:
+                return b.itemEstimatesBatch([0, keys.size], keys, vals, [0, items.size], items, self.KIND, self._capper)
+            except _lib.CmsError as e:
+                raise _map_error(e, "item")
+        return np.array([self._host_estimate(self._sim.itemSimilarities(int(i), keys), vals)
                          for i in items.tolist()], np.float32).reshape(-1)
 
     def estimatePreference(self, userID, itemID):
@@ -1141,6 +1204,14 @@ class GenericItemBasedRecommender:
                                                                         includeKnownItems, self._capper)
             except _lib.CmsError as e:
                 raise _map_error(e, "item")
+            return [[(int(items[u, j]), vals[u, j]) for j in range(int(cnt[u]))] for u in range(users.size)]
+        b = self._batch_sim()
+        if b is not None and isinstance(self._strategy, _CandidateItemsStrategy) and self._strategy.native is not None:
+            try:
+                cnt, items, vals = b.itemRecommendBatch(users, howMany, self.KIND, self._strategy.native,
+                                                        includeKnownItems, self._capper)
+            except _lib.CmsError as e:
+                raise _map_error(e, "user")
             return [[(int(items[u, j]), vals[u, j]) for j in range(int(cnt[u]))] for u in range(users.size)]
         out = []
         for u in users.tolist():
@@ -1202,6 +1273,32 @@ class GenericItemBasedRecommender:
 
     def refresh(self, alreadyRefreshed=None):
         self._capper = build_capper(self._model)
+        self._csr = None
+
+
+class GenericBooleanPrefItemBasedRecommender(GenericItemBasedRecommender):
+    """GenericBooleanPrefItemBasedRecommender(dataModel, similarity[,
+    candidateItemsStrategy, mostSimilarItemsCandidateItemsStrategy])
+    (T/impl/recommender/GenericBooleanPrefItemBasedRecommender.java): the
+    estimate is the sum of the candidate's similarities with the user's items
+    (:52-64) -- no preference value is read, nothing is capped.  The routes are
+    GenericItemBasedRecommender's: the boolean kind of the device batch with a
+    set similarity over this dataModel, bool_item_estimate on the host with any
+    other ItemSimilarity (a CosineCM included)."""
+
+    KIND = "boolean"
+
+    def __init__(self, dataModel, similarity, candidateItemsStrategy=None, mostSimilarItemsCandidateItemsStrategy=None):
+        super().__init__(dataModel, similarity, candidateItemsStrategy, mostSimilarItemsCandidateItemsStrategy)
+        self._capper = None
+
+    def _table(self):
+        return None  # the sketch table's batch computes the weighted estimate only
+
+    def _host_estimate(self, sims, vals):
+        return bool_item_estimate(sims)
+
+    def refresh(self, alreadyRefreshed=None):
         self._csr = None
 
 
