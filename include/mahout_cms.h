@@ -995,6 +995,33 @@ int cms_set_item_recommend_batch(cms_handle* h, int32_t measure, int32_t kind, i
                                  float cap_min, float cap_max, int32_t* out_counts, int64_t* out_items,
                                  float* out_values);
 
+/* ---- item-based recommenders over the co-rated similarities ----------------
+ * The two estimates above with a co-rated similarity as ItemSimilarity:
+ * measure is a CMS_SIM_* value of cms_common_*, and sim = itemSimilarity
+ * (candidate, preferred item) is that measure over the users that hold both
+ * items, the candidate first as the reference's itemSimilarities(candidate,
+ * preferredIDs) has it, under the handle's weighting.  A pair with nothing in
+ * common is NaN and gives no data point.  Every candidate's fp64 sums grow in
+ * preference order, one correctly rounded operation per data point, over
+ * similarities that have the reference's bits (cms_common_similarities), so an
+ * estimate has the reference's bits for all three measures and both kinds.
+ *
+ * Layout, validation and outputs are exactly those of
+ * cms_set_item_estimates_batch and cms_set_item_recommend_batch: CMS_E_STATE
+ * without a model attached with its values (cms_exact_attach_csr),
+ * CMS_E_PARAM for an unknown measure, kind or strategy, CMS_E_NO_SUCH_ID for a
+ * preferred item the model lacks, before anything is written; a candidate the
+ * model lacks reads NaN; a user without preferences is recommended nothing.
+ * Timing scope "common_item_estimate". */
+int cms_common_item_estimates_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n,
+                                    const int64_t* pref_offsets, const int64_t* pref_items, const float* pref_vals,
+                                    const int64_t* cand_offsets, const int64_t* cand_items, int32_t use_capper,
+                                    float cap_min, float cap_max, float* out);
+int cms_common_item_recommend_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* user_ids,
+                                    int32_t strategy, int32_t how_many, int32_t include_known, int32_t use_capper,
+                                    float cap_min, float cap_max, int32_t* out_counts, int64_t* out_items,
+                                    float* out_values);
+
 /* ---- instrumentation ------------------------------------------------------- */
 typedef struct cms_stats {
   uint32_t struct_size;     /* sizeof(cms_stats) as the caller compiled it: only fields that fit are written */

@@ -363,6 +363,7 @@ static int create_impl(const cms_params* p, bool per_owner, cms_handle** out) {
     h->tune.common_tile = std::max(0, num("CMS_COMMON_TILE", 0));
     h->tune.set_tile = std::max(0, num("CMS_SET_TILE", 0));
     h->tune.set_est_tile = std::max(0, num("CMS_SET_EST_TILE", 0));
+    h->tune.common_est_tile = std::max(0, num("CMS_COMMON_EST_TILE", 0));
   }
   h->per_owner = per_owner;
   h->f64 = f64;
@@ -1990,21 +1991,31 @@ int cms_set_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* i
   return CMS_OK;
 }
 
-// ---- the item-based recommenders over the set similarities (cms_set_item.hip) ----
+// ---- the item-based recommenders over the set similarities (cms_set_item.hip) and over the co-rated ones
+// (cms_common_item.hip): one body each for the estimates and the recommend call, the family's measure check
+// (set_require, common_require) and estimate batch (set_item_estimate_batch, common_item_estimate_batch) its
+// only varying parts ----
 
-static int set_item_require(cms_handle* h, const char* what, int32_t measure, int32_t kind) {
+struct ItemRoute {
+  int (*require)(cms_handle* h, const char* what, int32_t measure, int32_t side);
+  decltype(&set_item_estimate_batch) estimate;
+};
+static const ItemRoute kSetItemRoute{set_require, set_item_estimate_batch};
+static const ItemRoute kCommonItemRoute{common_require, common_item_estimate_batch};
+
+static int item_require(cms_handle* h, const ItemRoute& route, const char* what, int32_t measure, int32_t kind) {
   if (kind != CMS_ITEM_EST_WEIGHTED && kind != CMS_ITEM_EST_BOOLEAN)
     return set_error(CMS_E_PARAM, "%s: unknown kind %d", what, (int)kind);
-  return set_require(h, what, measure, CMS_SIDE_KEY);
+  return route.require(h, what, measure, CMS_SIDE_KEY);
 }
 
-int cms_set_item_estimates_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* pref_offsets,
-                                 const int64_t* pref_items, const float* pref_vals, const int64_t* cand_offsets,
-                                 const int64_t* cand_items, int32_t use_capper, float cap_min, float cap_max,
-                                 float* out) {
+static int item_route_estimates_batch(cms_handle* h, const ItemRoute& route, const char* what, int32_t measure,
+                                      int32_t kind, int64_t n, const int64_t* pref_offsets, const int64_t* pref_items,
+                                      const float* pref_vals, const int64_t* cand_offsets, const int64_t* cand_items,
+                                      int32_t use_capper, float cap_min, float cap_max, float* out) {
   if (!h || n < 0 || (n > 0 && (!pref_offsets || !cand_offsets))) return set_error(CMS_E_PARAM, "null argument");
   Guard g(h);
-  int rc = set_item_require(h, "cms_set_item_estimates_batch", measure, kind);
+  int rc = item_require(h, route, what, measure, kind);
   if (rc) return rc;
   if (n == 0) return CMS_OK;
   if ((rc = check_offsets("pref_offsets", pref_offsets, n)) || (rc = check_offsets("cand_offsets", cand_offsets, n)))
@@ -2013,21 +2024,21 @@ int cms_set_item_estimates_batch(cms_handle* h, int32_t measure, int32_t kind, i
   if ((M > 0 && (!pref_items || (kind == CMS_ITEM_EST_WEIGHTED && !pref_vals))) || (Q > 0 && (!cand_items || !out)))
     return set_error(CMS_E_PARAM, "null argument");
   if (Q >= (int64_t(1) << 31)) return set_error(CMS_E_PARAM, "too many candidate items in one batch");
-  return set_item_estimate_batch(h, measure, kind, n, pref_offsets, pref_items, pref_vals, cand_offsets, cand_items,
-                                 use_capper, cap_min, cap_max, out);
+  return route.estimate(h, measure, kind, n, pref_offsets, pref_items, pref_vals, cand_offsets, cand_items, use_capper,
+                        cap_min, cap_max, out);
 }
 
-int cms_set_item_recommend_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* user_ids,
-                                 int32_t strategy, int32_t how_many, int32_t include_known, int32_t use_capper,
-                                 float cap_min, float cap_max, int32_t* out_counts, int64_t* out_items,
-                                 float* out_values) {
+static int item_route_recommend_batch(cms_handle* h, const ItemRoute& route, const char* what, int32_t measure,
+                                      int32_t kind, int64_t n, const int64_t* user_ids, int32_t strategy,
+                                      int32_t how_many, int32_t include_known, int32_t use_capper, float cap_min,
+                                      float cap_max, int32_t* out_counts, int64_t* out_items, float* out_values) {
   if (!h || n < 0 || (n > 0 && (!user_ids || !out_counts || !out_items || !out_values)))
     return set_error(CMS_E_PARAM, "null argument");
   if (how_many < 1) return set_error(CMS_E_PARAM, "howMany must be at least 1");
   if (strategy != 0 && strategy != 1)
     return set_error(CMS_E_PARAM, "strategy must be 0 (preferred items' neighbourhood) or 1 (all unknown items)");
   Guard g(h);
-  int rc = set_item_require(h, "cms_set_item_recommend_batch", measure, kind);
+  int rc = item_require(h, route, what, measure, kind);
   if (rc) return rc;
   if (n == 0) return CMS_OK;
   // the attached model is the DataModel: owner rows are its rows
@@ -2065,8 +2076,8 @@ int cms_set_item_recommend_batch(cms_handle* h, int32_t measure, int32_t kind, i
     std::copy(cand[(size_t)u].begin(), cand[(size_t)u].end(), c_items.begin() + c_off[(size_t)u]);
   }
   std::vector<float> est(c_items.size());
-  if ((rc = set_item_estimate_batch(h, measure, kind, n, p_off.data(), p_items.data(), p_vals.data(), c_off.data(),
-                                    c_items.data(), use_capper, cap_min, cap_max, est.data())))
+  if ((rc = route.estimate(h, measure, kind, n, p_off.data(), p_items.data(), p_vals.data(), c_off.data(),
+                           c_items.data(), use_capper, cap_min, cap_max, est.data())))
     return rc;
   parallel_users(n, threads, [&](int64_t u) {
     const int64_t o = c_off[(size_t)u];
@@ -2074,6 +2085,41 @@ int cms_set_item_recommend_batch(cms_handle* h, int32_t measure, int32_t kind, i
                                         out_items + u * (int64_t)how_many, out_values + u * (int64_t)how_many);
   });
   return CMS_OK;
+}
+
+int cms_set_item_estimates_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* pref_offsets,
+                                 const int64_t* pref_items, const float* pref_vals, const int64_t* cand_offsets,
+                                 const int64_t* cand_items, int32_t use_capper, float cap_min, float cap_max,
+                                 float* out) {
+  return item_route_estimates_batch(h, kSetItemRoute, "cms_set_item_estimates_batch", measure, kind, n, pref_offsets,
+                                    pref_items, pref_vals, cand_offsets, cand_items, use_capper, cap_min, cap_max, out);
+}
+
+int cms_set_item_recommend_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* user_ids,
+                                 int32_t strategy, int32_t how_many, int32_t include_known, int32_t use_capper,
+                                 float cap_min, float cap_max, int32_t* out_counts, int64_t* out_items,
+                                 float* out_values) {
+  return item_route_recommend_batch(h, kSetItemRoute, "cms_set_item_recommend_batch", measure, kind, n, user_ids,
+                                    strategy, how_many, include_known, use_capper, cap_min, cap_max, out_counts,
+                                    out_items, out_values);
+}
+
+int cms_common_item_estimates_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n,
+                                    const int64_t* pref_offsets, const int64_t* pref_items, const float* pref_vals,
+                                    const int64_t* cand_offsets, const int64_t* cand_items, int32_t use_capper,
+                                    float cap_min, float cap_max, float* out) {
+  return item_route_estimates_batch(h, kCommonItemRoute, "cms_common_item_estimates_batch", measure, kind, n,
+                                    pref_offsets, pref_items, pref_vals, cand_offsets, cand_items, use_capper, cap_min,
+                                    cap_max, out);
+}
+
+int cms_common_item_recommend_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* user_ids,
+                                    int32_t strategy, int32_t how_many, int32_t include_known, int32_t use_capper,
+                                    float cap_min, float cap_max, int32_t* out_counts, int64_t* out_items,
+                                    float* out_values) {
+  return item_route_recommend_batch(h, kCommonItemRoute, "cms_common_item_recommend_batch", measure, kind, n, user_ids,
+                                    strategy, how_many, include_known, use_capper, cap_min, cap_max, out_counts,
+                                    out_items, out_values);
 }
 
 extern "C++" {

@@ -8,6 +8,7 @@
 
 #include "cms_exact.h"
 #include "cms_internal.h"
+#include "cms_set_item_plan.h"
 
 namespace cms {
 
@@ -89,5 +90,27 @@ struct CommonPairArgs {
   double* out;
   int64_t ld;
 };
+
+// The item-based estimate kernels' argument (k_set_item_estimate, k_common_item_estimate): one batch's preferences
+// and the plan of cms_set_item_plan.h.
+struct SetItemArgs {
+  const int64_t* pref_off;   // [n + 1] user u's preferred items: pref_idx / pref_val [pref_off[u], pref_off[u + 1])
+  const int32_t* pref_idx;   // dense item indices, in preference order
+  const float* pref_val;     // (weighted only)
+  const SetItemTile* tiles;
+  const int32_t* slot_item;  // [S]
+  float* est;                // [S]
+  int32_t T, use_capper;
+  float lo, hi;
+};
+
+// The host body of one item-based estimate batch (cms_set_item.hip), shaped as set_item_estimate_batch: `launch`
+// runs the estimating kernel of (measure, kind) over the plan's ntiles tiles of T items on the handle's stream.
+using ItemEstLaunch = int (*)(cms_handle* h, int32_t measure, int32_t kind, const CommonSide& v, const SetItemArgs& g,
+                              int64_t ntiles);
+int item_estimate_batch(cms_handle* h, ItemEstLaunch launch, int T, int32_t measure, int32_t kind, int64_t n,
+                        const int64_t* pref_offsets, const int64_t* pref_keys, const float* pref_vals,
+                        const int64_t* cand_offsets, const int64_t* cand_keys, int32_t use_capper, float cap_min,
+                        float cap_max, float* out);
 
 }  // namespace cms

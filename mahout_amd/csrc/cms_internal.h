@@ -234,6 +234,7 @@ struct Tunables {
   int common_tile = 0;      // CMS_COMMON_TILE: candidates per workgroup of k_common_tile, a multiple of 64 (0: the measure's default)
   int set_tile = 0;         // CMS_SET_TILE: candidates per workgroup of k_set_tile, a multiple of 64 (0: kSetTileDefault)
   int set_est_tile = 0;     // CMS_SET_EST_TILE: items per workgroup of k_set_item_estimate, a multiple of 64 (0: the kind's default)
+  int common_est_tile = 0;  // CMS_COMMON_EST_TILE: items per workgroup of k_common_item_estimate, a multiple of 64 (0: the default of the measure and kind)
 };
 struct ExactModel;  // the attached DataModel of the exact cosine (cms_exact.hip)
 }  // namespace cms
@@ -776,6 +777,12 @@ int set_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* idx, 
 int set_item_estimate_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* pref_offsets,
                             const int64_t* pref_keys, const float* pref_vals, const int64_t* cand_offsets,
                             const int64_t* cand_keys, int32_t use_capper, float cap_min, float cap_max, float* out);
+// ---- cms_common_item.hip: the item-based recommenders' estimates over the co-rated similarities ----
+// set_item_estimate_batch with the similarity of (candidate, preferred item) one of the co-rated measures
+// (measure: CMS_SIM_*, validated by the caller), the candidate as X
+int common_item_estimate_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* pref_offsets,
+                               const int64_t* pref_keys, const float* pref_vals, const int64_t* cand_offsets,
+                               const int64_t* cand_keys, int32_t use_capper, float cap_min, float cap_max, float* out);
 // ---- cms_f64.hip (CMS_COUNTER_F64) ----
 int f64_ingest_csr(cms_handle* h, const int64_t* d_off, const int64_t* d_key, const float* d_val);
 int f64_ingest_coo_host(cms_handle* h, const int64_t* owner, const int64_t* key, const float* val, int64_t np);

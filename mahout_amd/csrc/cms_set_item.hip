@@ -67,17 +67,6 @@ namespace cms {
 
 constexpr int kSetItemThreads = 512;  // 8 waves; two workgroups per CU at the default tiles
 
-struct SetItemArgs {
-  const int64_t* pref_off;   // [n + 1] user u's preferred items: pref_idx / pref_val [pref_off[u], pref_off[u + 1])
-  const int32_t* pref_idx;   // dense item indices, in preference order
-  const float* pref_val;     // (weighted only)
-  const SetItemTile* tiles;
-  const int32_t* slot_item;  // [S]
-  float* est;                // [S]
-  int32_t T, use_capper;
-  float lo, hi;
-};
-
 template <int MEASURE, int KIND>
 __global__ __launch_bounds__(kSetItemThreads) void k_set_item_estimate(CommonSide v, SetItemArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char set_item_lds[];
@@ -197,9 +186,27 @@ static int launch_set_item(cms_handle* h, int32_t measure, const CommonSide& v, 
   }
 }
 
+static int launch_set_item_kind(cms_handle* h, int32_t measure, int32_t kind, const CommonSide& v, const SetItemArgs& g,
+                                int64_t ntiles) {
+  return kind == kItemEstWeighted ? launch_set_item<kItemEstWeighted>(h, measure, v, g, ntiles)
+                                  : launch_set_item<kItemEstBoolean>(h, measure, v, g, ntiles);
+}
+
 int set_item_estimate_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* pref_offsets,
                             const int64_t* pref_keys, const float* pref_vals, const int64_t* cand_offsets,
                             const int64_t* cand_keys, int32_t use_capper, float cap_min, float cap_max, float* out) {
+  return item_estimate_batch(h, launch_set_item_kind, set_item_tile_for(kind, h->tune.set_est_tile), measure, kind, n,
+                             pref_offsets, pref_keys, pref_vals, cand_offsets, cand_keys, use_capper, cap_min, cap_max,
+                             out);
+}
+
+// The host body of one batch, whichever kernel estimates (k_set_item_estimate here, k_common_item_estimate in
+// cms_common_item.hip): the preferred keys' dense indices, the plan at tile T, the uploads, `launch` over the
+// plan's tiles, and the slots back in the caller's positions.
+int item_estimate_batch(cms_handle* h, ItemEstLaunch launch, int T, int32_t measure, int32_t kind, int64_t n,
+                        const int64_t* pref_offsets, const int64_t* pref_keys, const float* pref_vals,
+                        const int64_t* cand_offsets, const int64_t* cand_keys, int32_t use_capper, float cap_min,
+                        float cap_max, float* out) {
   ExactModel& m = *h->exact;
   const int64_t M = pref_offsets[n], Q = cand_offsets[n];
   // a preferred item the model lacks would throw NoSuchItemException from itemSimilarities: before anything is written
@@ -208,7 +215,6 @@ int set_item_estimate_batch(cms_handle* h, int32_t measure, int32_t kind, int64_
   if (missing >= 0)
     return set_error(CMS_E_NO_SUCH_ID, "no such key %lld in the attached model", (long long)pref_keys[missing]);
   if (Q == 0) return CMS_OK;
-  const int T = set_item_tile_for(kind, h->tune.set_est_tile);
   SetItemPlan plan;
   set_item_plan(m.ids, n, cand_offsets, cand_keys, T, plan, [](int64_t users, auto f) {
     parallel_users(users, (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency())), f);
@@ -228,10 +234,7 @@ int set_item_estimate_batch(cms_handle* h, int32_t measure, int32_t kind, int64_
                           m.e_tiles.as<SetItemTile>(), m.e_slot.as<int32_t>(), m.e_est.as<float>(),
                           (int32_t)T,                  use_capper,             cap_min,
                           cap_max};
-      const CommonSide v = common_side(h, CMS_SIDE_KEY);
-      rc = kind == kItemEstWeighted ? launch_set_item<kItemEstWeighted>(h, measure, v, g, (int64_t)plan.tiles.size())
-                                    : launch_set_item<kItemEstBoolean>(h, measure, v, g, (int64_t)plan.tiles.size());
-      if (rc) return rc;
+      if ((rc = launch(h, measure, kind, common_side(h, CMS_SIDE_KEY), g, (int64_t)plan.tiles.size()))) return rc;
       CMS_HIP(hipMemcpyAsync(est.data(), m.e_est.ptr, sizeof(float) * S, hipMemcpyDeviceToHost, h->stream));
       return CMS_OK;
     }();

@@ -566,14 +566,9 @@ class SketchTable:
     # -- item-based recommenders over the set similarities --
     ITEM_EST_KINDS = {"weighted": 0, "boolean": 1}  # CMS_ITEM_EST_*
 
-    def set_item_estimates_batch(self, pref_offsets, pref_items, pref_vals, cand_offsets, cand_items,
-                                 measure="loglikelihood", kind="boolean", capper=None):
-        """cms_set_item_estimates_batch: doEstimatePreference of
-        GenericItemBasedRecommender (kind="weighted") or
-        GenericBooleanPrefItemBasedRecommender (kind="boolean") with a set
-        similarity over the attached model's items, shaped as
-        item_estimates_batch; pref_vals may be None for "boolean".  One float32
-        per candidate; a candidate the model lacks reads NaN."""
+    def _item_estimates_batch(self, call, measure, kind, pref_offsets, pref_items, pref_vals, cand_offsets, cand_items,
+                              capper):
+        """cms_set_item_estimates_batch or its co-rated twin: the arrays checked and laid out, one float32 per candidate."""
         pi = np.ascontiguousarray(pref_items, np.int64).reshape(-1)
         pv = None if pref_vals is None else np.ascontiguousarray(pref_vals, np.float32).reshape(-1)
         ci = np.ascontiguousarray(cand_items, np.int64).reshape(-1)
@@ -582,18 +577,12 @@ class SketchTable:
         co = self._csr("cand_offsets", cand_offsets, n, ci)
         out = np.zeros(ci.size, np.float32)
         lo, hi = capper if capper is not None else (0.0, 0.0)
-        ms, _ = self._set_args(measure, "key")
-        check(self._lib.cms_set_item_estimates_batch(self._h, ms, int(self.ITEM_EST_KINDS.get(kind, kind)), n, _ptr(po),
-                                                     _ptr(pi), _ptr(pv), _ptr(co), _ptr(ci), int(capper is not None),
-                                                     float(lo), float(hi), _ptr(out)))
+        check(call(self._h, measure, int(self.ITEM_EST_KINDS.get(kind, kind)), n, _ptr(po), _ptr(pi), _ptr(pv), _ptr(co),
+                   _ptr(ci), int(capper is not None), float(lo), float(hi), _ptr(out)))
         return out
 
-    def set_item_recommend_batch(self, user_ids, how_many, measure="loglikelihood", kind="boolean",
-                                 strategy="preferred", include_known=False, capper=None):
-        """cms_set_item_recommend_batch: recommend() of those recommenders for
-        every user of user_ids, the attached model as the DataModel (kind
-        "weighted" reads the values it was attached with).  Returns (counts
-        [n], items [n][how_many], values [n][how_many] float32)."""
+    def _item_recommend_batch(self, call, measure, kind, user_ids, how_many, strategy, include_known, capper):
+        """cms_set_item_recommend_batch or its co-rated twin: (counts [n], items [n][how_many], values float32)."""
         us = np.ascontiguousarray(user_ids, np.int64).reshape(-1)
         if how_many < 1:
             raise ValueError("howMany must be at least 1")
@@ -601,12 +590,49 @@ class SketchTable:
         items = np.full((us.size, how_many), -1, np.int64)
         vals = np.full((us.size, how_many), np.nan, np.float32)
         lo, hi = capper if capper is not None else (0.0, 0.0)
-        ms, _ = self._set_args(measure, "key")
-        check(self._lib.cms_set_item_recommend_batch(self._h, ms, int(self.ITEM_EST_KINDS.get(kind, kind)), us.size,
-                                                     _ptr(us), int(self.ITEM_STRATEGIES.get(strategy, strategy)),
-                                                     int(how_many), int(bool(include_known)), int(capper is not None),
-                                                     float(lo), float(hi), _ptr(counts), _ptr(items), _ptr(vals)))
+        check(call(self._h, measure, int(self.ITEM_EST_KINDS.get(kind, kind)), us.size, _ptr(us),
+                   int(self.ITEM_STRATEGIES.get(strategy, strategy)), int(how_many), int(bool(include_known)),
+                   int(capper is not None), float(lo), float(hi), _ptr(counts), _ptr(items), _ptr(vals)))
         return counts, items, vals
+
+    def set_item_estimates_batch(self, pref_offsets, pref_items, pref_vals, cand_offsets, cand_items,
+                                 measure="loglikelihood", kind="boolean", capper=None):
+        """cms_set_item_estimates_batch: doEstimatePreference of
+        GenericItemBasedRecommender (kind="weighted") or
+        GenericBooleanPrefItemBasedRecommender (kind="boolean") with a set
+        similarity over the attached model's items, shaped as
+        item_estimates_batch; pref_vals may be None for "boolean".  One float32
+        per candidate; a candidate the model lacks reads NaN."""
+        return self._item_estimates_batch(self._lib.cms_set_item_estimates_batch, self._set_args(measure, "key")[0], kind,
+                                          pref_offsets, pref_items, pref_vals, cand_offsets, cand_items, capper)
+
+    def set_item_recommend_batch(self, user_ids, how_many, measure="loglikelihood", kind="boolean",
+                                 strategy="preferred", include_known=False, capper=None):
+        """cms_set_item_recommend_batch: recommend() of those recommenders for
+        every user of user_ids, the attached model as the DataModel (kind
+        "weighted" reads the values it was attached with).  Returns (counts
+        [n], items [n][how_many], values [n][how_many] float32)."""
+        return self._item_recommend_batch(self._lib.cms_set_item_recommend_batch, self._set_args(measure, "key")[0], kind,
+                                          user_ids, how_many, strategy, include_known, capper)
+
+    # -- item-based recommenders over the co-rated similarities --
+    def common_item_estimates_batch(self, pref_offsets, pref_items, pref_vals, cand_offsets, cand_items,
+                                    measure="pearson", kind="weighted", capper=None):
+        """cms_common_item_estimates_batch: set_item_estimates_batch with a
+        co-rated similarity ("uncentered_cosine", "pearson", "euclidean") over
+        the model attached by attach_exact, the candidate first in every pair,
+        under the table's weighting.  The reference's bits for every measure."""
+        return self._item_estimates_batch(self._lib.cms_common_item_estimates_batch,
+                                          self._common_args(measure, "key")[0], kind, pref_offsets, pref_items,
+                                          pref_vals, cand_offsets, cand_items, capper)
+
+    def common_item_recommend_batch(self, user_ids, how_many, measure="pearson", kind="weighted", strategy="preferred",
+                                    include_known=False, capper=None):
+        """cms_common_item_recommend_batch: set_item_recommend_batch over a
+        co-rated similarity, the attached model (attach_exact) as the DataModel."""
+        return self._item_recommend_batch(self._lib.cms_common_item_recommend_batch,
+                                          self._common_args(measure, "key")[0], kind, user_ids, how_many, strategy,
+                                          include_known, capper)
 
     # -- anonymous profiles: preferences that are no row of the table --
     @staticmethod

@@ -632,6 +632,21 @@ class _CommonSimilarity(CosineSimilarity):
     def recommendBatch(self, userIDs, nb_offsets, neighborIDs, modelCSR, howMany, includeKnownItems=False, capper=None):
         raise NotImplementedError("the device batch recommend takes its similarities from the full-norm cosine only")
 
+    # the item-based recommenders' device route (GenericItemBasedRecommender looks for these three)
+    def servesItemModel(self, dataModel):
+        """Whether the attached model is dataModel: its rows are then the recommender's users."""
+        return dataModel is self._model
+
+    def itemEstimatesBatch(self, pref_offsets, pref_items, pref_vals, cand_offsets, cand_items, kind, capper=None):
+        """doEstimatePreference for many users in one device batch (cms_common_item_estimates_batch)."""
+        return self._table.common_item_estimates_batch(pref_offsets, pref_items, pref_vals, cand_offsets, cand_items,
+                                                       self.MEASURE, kind, capper)
+
+    def itemRecommendBatch(self, userIDs, howMany, kind, strategy, includeKnownItems=False, capper=None):
+        """recommend for many users (cms_common_item_recommend_batch): (counts, items, values)."""
+        return self._table.common_item_recommend_batch(userIDs, howMany, self.MEASURE, kind, strategy,
+                                                       includeKnownItems, capper)
+
 
 class PearsonCorrelationSimilarity(_CommonSimilarity):
     """PearsonCorrelationSimilarity(DataModel[, Weighting]) (T/impl/similarity/PearsonCorrelationSimilarity.java)."""
@@ -1080,9 +1095,10 @@ class GenericItemBasedRecommender:
     those calls refuse (per-owner shapes, fp64 counters), is served through
     itemSimilarities per candidate and item_estimate on the host.  A similarity
     that offers itemEstimatesBatch / itemRecommendBatch over this very
-    dataModel (the set similarities: Tanimoto, log-likelihood, city block) puts
-    the estimates of a call, and with a built-in strategy the whole
-    recommend_all, into one device batch (cms_set_item_*).  That recommend_all
+    dataModel (the set similarities: Tanimoto, log-likelihood, city block; the
+    co-rated ones: Pearson, uncentered cosine, Euclidean) puts the estimates of
+    a call, and with a built-in strategy the whole recommend_all, into one
+    device batch (cms_set_item_*, cms_common_item_*).  That recommend_all
     reads the preferences, and the weighted kind their values, from the model
     as the similarity attached it, while doEstimatePreferences and the host
     route read dataModel itself: after a change of the model, refresh() the
