@@ -950,6 +950,43 @@ int cms_set_pairs(cms_handle* h, int32_t measure, int32_t side, const int64_t* i
 int cms_set_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* ids, int64_t nq, int32_t k,
                   int64_t* out_ids, double* out_scores, int32_t* out_counts);
 
+/* ---- user-based recommenders over the co-rated and the set similarities -----
+ * cms_exact_estimate_preferences_batch and cms_exact_recommend_batch with
+ * userSimilarity(user, neighbour) one of the co-rated measures (family
+ * CMS_FAMILY_COMMON, measure CMS_SIM_*) or of the set measures (CMS_FAMILY_SET,
+ * CMS_SET_*) over the attached model's owner side, and the estimate of
+ *   CMS_NB_GENERIC  GenericUserBasedRecommender.doEstimatePreference, sim == null
+ *     (:134-184): a NaN similarity is skipped, fewer than two data points give
+ *     NaN, (float)(preference / totalSimilarity), then the capper when
+ *     use_capper;
+ *   CMS_NB_BOOLEAN  GenericBooleanPrefUserBasedRecommender.doEstimatePreference
+ *     (:45-61): a float totalSimilarity += (float) similarity for every neighbour
+ *     that is not the user and holds the item -- a NaN similarity is not skipped
+ *     and makes the estimate NaN; NaN when nobody holds the item; no count rule,
+ *     no capper: use_capper and the caps are not read.
+ * The neighbourhood is walked in the caller's order, a neighbour named twice
+ * counts twice, an empty neighbourhood gives NaN.  A model attached without
+ * values carries 1.0 per entry.  The similarities are the family's pair
+ * kernel's, so the co-rated measures, Tanimoto and city block give the
+ * reference's estimate bit for bit and log-likelihood within the freedom of its
+ * similarity.  Argument rules and errors as the cms_exact_* namesakes;
+ * CMS_E_STATE without a model, CMS_E_PARAM for an unknown family, measure or
+ * kind, CMS_E_NO_SUCH_ID for an unknown user or neighbour, before anything is
+ * written.  Timing scopes "nb_pairs", "nb_estimate". */
+#define CMS_FAMILY_COMMON 0
+#define CMS_FAMILY_SET 1
+#define CMS_NB_GENERIC 0
+#define CMS_NB_BOOLEAN 1
+int cms_neighbor_estimate_preferences_batch(cms_handle* h, int32_t family, int32_t measure, int32_t kind, int64_t n,
+                                            const int64_t* user_ids, const int64_t* nb_offsets,
+                                            const int64_t* neighbor_ids, const int64_t* item_offsets,
+                                            const int64_t* item_keys, int32_t use_capper, float cap_min, float cap_max,
+                                            float* out);
+int cms_neighbor_recommend_batch(cms_handle* h, int32_t family, int32_t measure, int32_t kind, int64_t n,
+                                 const int64_t* user_ids, const int64_t* nb_offsets, const int64_t* neighbor_ids,
+                                 int32_t how_many, int32_t include_known, int32_t use_capper, float cap_min,
+                                 float cap_max, int32_t* out_counts, int64_t* out_items, float* out_values);
+
 /* ---- item-based recommenders over the set similarities ----------------------
  * The estimates of the reference's item-based recommenders with one of the set
  * similarities as ItemSimilarity, over the attached model's key side (its

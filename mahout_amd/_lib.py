@@ -63,6 +63,7 @@ EXPORTS = [
     "cms_set_similarities", "cms_set_pairs", "cms_set_top_k",
     "cms_set_item_estimates_batch", "cms_set_item_recommend_batch",
     "cms_common_item_estimates_batch", "cms_common_item_recommend_batch",
+    "cms_neighbor_estimate_preferences_batch", "cms_neighbor_recommend_batch",
 ]
 
 
@@ -235,6 +236,10 @@ _SIGS = {
                                                ctypes.c_float, _vp]),
     "cms_common_item_recommend_batch": (_int, [_vp, _i32, _i32, _i64, _vp, _i32, _i32, _i32, _i32, ctypes.c_float,
                                                ctypes.c_float, _vp, _vp, _vp]),
+    "cms_neighbor_estimate_preferences_batch": (_int, [_vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32,
+                                                       ctypes.c_float, ctypes.c_float, _vp]),
+    "cms_neighbor_recommend_batch": (_int, [_vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i32, _i32, _i32,
+                                            ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -364,6 +364,7 @@ static int create_impl(const cms_params* p, bool per_owner, cms_handle** out) {
     h->tune.set_tile = std::max(0, num("CMS_SET_TILE", 0));
     h->tune.set_est_tile = std::max(0, num("CMS_SET_EST_TILE", 0));
     h->tune.common_est_tile = std::max(0, num("CMS_COMMON_EST_TILE", 0));
+    h->tune.nb_est_tile = std::max(0, num("CMS_NB_EST_TILE", 0));
   }
   h->per_owner = per_owner;
   h->f64 = f64;
@@ -1813,10 +1814,14 @@ static int exact_batch_rows(cms_handle* h, int64_t n, const int64_t* user_ids, c
   return CMS_OK;
 }
 
-int cms_exact_estimate_preferences_batch(cms_handle* h, int64_t n, const int64_t* user_ids, const int64_t* nb_offsets,
-                                         const int64_t* neighbor_ids, const int64_t* item_offsets,
-                                         const int64_t* item_keys, int32_t use_capper, float cap_min, float cap_max,
-                                         float* out) {
+// The bodies of the user-based estimate and recommend calls over the attached model, whichever similarity scores
+// the neighbours: require() checks the call's own arguments and the model under the handle's lock, and
+// estimate(user_rows, nb_rows, item_offsets, item_keys, out) is exact_estimate_batch or nb_estimate_batch.
+extern "C++" {
+template <class Require, class Estimate>
+static int user_estimates_body(cms_handle* h, int64_t n, const int64_t* user_ids, const int64_t* nb_offsets,
+                               const int64_t* neighbor_ids, const int64_t* item_offsets, const int64_t* item_keys,
+                               float* out, Require require, Estimate estimate) {
   if (!h || n < 0 || (n > 0 && (!user_ids || !nb_offsets || !item_offsets)))
     return set_error(CMS_E_PARAM, "null argument");
   if (n == 0) return CMS_OK;
@@ -1828,18 +1833,18 @@ int cms_exact_estimate_preferences_batch(cms_handle* h, int64_t n, const int64_t
   if ((M > 0 && !neighbor_ids) || (Q > 0 && (!item_keys || !out))) return set_error(CMS_E_PARAM, "null argument");
   if (Q >= (int64_t(1) << 31)) return set_error(CMS_E_PARAM, "too many candidate items in one batch");
   Guard g(h);
-  int rc = exact_require(h, "cms_exact_estimate_preferences_batch");
+  int rc = require();
   if (rc) return rc;
   std::vector<int64_t> user_rows, nb_rows;
   if ((rc = exact_batch_rows(h, n, user_ids, nb_offsets, neighbor_ids, user_rows, nb_rows))) return rc;
-  return exact_estimate_batch(h, n, user_rows.data(), nb_offsets, nb_rows.data(), item_offsets, item_keys, use_capper,
-                              cap_min, cap_max, out);
+  return estimate(user_rows.data(), nb_rows.data(), item_offsets, item_keys, out);
 }
 
-int cms_exact_recommend_batch(cms_handle* h, int64_t n, const int64_t* user_ids, const int64_t* nb_offsets,
-                              const int64_t* neighbor_ids, int32_t how_many, int32_t include_known, int32_t use_capper,
-                              float cap_min, float cap_max, int32_t* out_counts, int64_t* out_items,
-                              float* out_values) {
+template <class Require, class Estimate>
+static int user_recommend_body(cms_handle* h, int64_t n, const int64_t* user_ids, const int64_t* nb_offsets,
+                               const int64_t* neighbor_ids, int32_t how_many, int32_t include_known,
+                               int32_t* out_counts, int64_t* out_items, float* out_values, Require require,
+                               Estimate estimate) {
   if (!h || n < 0 || (n > 0 && (!user_ids || !nb_offsets || !out_counts || !out_items || !out_values)))
     return set_error(CMS_E_PARAM, "null argument");
   if (how_many < 1) return set_error(CMS_E_PARAM, "howMany must be at least 1");
@@ -1849,7 +1854,7 @@ int cms_exact_recommend_batch(cms_handle* h, int64_t n, const int64_t* user_ids,
     if (nb_offsets[u + 1] < nb_offsets[u]) return set_error(CMS_E_PARAM, "nb_offsets must not decrease");
   if (nb_offsets[n] > 0 && !neighbor_ids) return set_error(CMS_E_PARAM, "null argument");
   Guard g(h);
-  int rc = exact_require(h, "cms_exact_recommend_batch");
+  int rc = require();
   if (rc) return rc;
   // the attached model is the DataModel: owner rows are its rows
   std::vector<int64_t> user_rows, nb_rows;
@@ -1861,9 +1866,35 @@ int cms_exact_recommend_batch(cms_handle* h, int64_t n, const int64_t* user_ids,
                         [&](const int64_t* it_off, const int64_t* keys, float* est) {
                           if (it_off[n] >= (int64_t(1) << 31))
                             return set_error(CMS_E_PARAM, "too many candidate items in one batch");
-                          return exact_estimate_batch(h, n, user_rows.data(), nb_offsets, nb_rows.data(), it_off, keys,
-                                                      use_capper, cap_min, cap_max, est);
+                          return estimate(user_rows.data(), nb_rows.data(), it_off, keys, est);
                         });
+}
+}  // extern "C++"
+
+int cms_exact_estimate_preferences_batch(cms_handle* h, int64_t n, const int64_t* user_ids, const int64_t* nb_offsets,
+                                         const int64_t* neighbor_ids, const int64_t* item_offsets,
+                                         const int64_t* item_keys, int32_t use_capper, float cap_min, float cap_max,
+                                         float* out) {
+  return user_estimates_body(
+      h, n, user_ids, nb_offsets, neighbor_ids, item_offsets, item_keys, out,
+      [&] { return exact_require(h, "cms_exact_estimate_preferences_batch"); },
+      [&](const int64_t* user_rows, const int64_t* nb_rows, const int64_t* it_off, const int64_t* keys, float* est) {
+        return exact_estimate_batch(h, n, user_rows, nb_offsets, nb_rows, it_off, keys, use_capper, cap_min, cap_max,
+                                    est);
+      });
+}
+
+int cms_exact_recommend_batch(cms_handle* h, int64_t n, const int64_t* user_ids, const int64_t* nb_offsets,
+                              const int64_t* neighbor_ids, int32_t how_many, int32_t include_known, int32_t use_capper,
+                              float cap_min, float cap_max, int32_t* out_counts, int64_t* out_items,
+                              float* out_values) {
+  return user_recommend_body(
+      h, n, user_ids, nb_offsets, neighbor_ids, how_many, include_known, out_counts, out_items, out_values,
+      [&] { return exact_require(h, "cms_exact_recommend_batch"); },
+      [&](const int64_t* user_rows, const int64_t* nb_rows, const int64_t* it_off, const int64_t* keys, float* est) {
+        return exact_estimate_batch(h, n, user_rows, nb_offsets, nb_rows, it_off, keys, use_capper, cap_min, cap_max,
+                                    est);
+      });
 }
 
 // ---- the co-rated similarities over the attached DataModel (cms_common.hip) ----
@@ -1989,6 +2020,43 @@ int cms_set_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* i
   CMS_HIP(hipMemcpyAsync(out_counts, o_cnt.ptr, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
   CMS_HIP(hipStreamSynchronize(h->stream));
   return CMS_OK;
+}
+
+// ---- the user-based recommenders over the co-rated and the set similarities (cms_neighbor.hip) ----
+
+static int nb_require(cms_handle* h, const char* what, int32_t family, int32_t measure, int32_t kind) {
+  if (family != CMS_FAMILY_COMMON && family != CMS_FAMILY_SET)
+    return set_error(CMS_E_PARAM, "%s: unknown family %d", what, (int)family);
+  if (kind != CMS_NB_GENERIC && kind != CMS_NB_BOOLEAN) return set_error(CMS_E_PARAM, "%s: unknown kind %d", what, (int)kind);
+  return family == CMS_FAMILY_COMMON ? common_require(h, what, measure, CMS_SIDE_OWNER)
+                                     : set_require(h, what, measure, CMS_SIDE_OWNER);
+}
+
+int cms_neighbor_estimate_preferences_batch(cms_handle* h, int32_t family, int32_t measure, int32_t kind, int64_t n,
+                                            const int64_t* user_ids, const int64_t* nb_offsets,
+                                            const int64_t* neighbor_ids, const int64_t* item_offsets,
+                                            const int64_t* item_keys, int32_t use_capper, float cap_min, float cap_max,
+                                            float* out) {
+  return user_estimates_body(
+      h, n, user_ids, nb_offsets, neighbor_ids, item_offsets, item_keys, out,
+      [&] { return nb_require(h, "cms_neighbor_estimate_preferences_batch", family, measure, kind); },
+      [&](const int64_t* user_rows, const int64_t* nb_rows, const int64_t* it_off, const int64_t* keys, float* est) {
+        return nb_estimate_batch(h, family, measure, kind, n, user_rows, nb_offsets, nb_rows, it_off, keys, use_capper,
+                                 cap_min, cap_max, est);
+      });
+}
+
+int cms_neighbor_recommend_batch(cms_handle* h, int32_t family, int32_t measure, int32_t kind, int64_t n,
+                                 const int64_t* user_ids, const int64_t* nb_offsets, const int64_t* neighbor_ids,
+                                 int32_t how_many, int32_t include_known, int32_t use_capper, float cap_min,
+                                 float cap_max, int32_t* out_counts, int64_t* out_items, float* out_values) {
+  return user_recommend_body(
+      h, n, user_ids, nb_offsets, neighbor_ids, how_many, include_known, out_counts, out_items, out_values,
+      [&] { return nb_require(h, "cms_neighbor_recommend_batch", family, measure, kind); },
+      [&](const int64_t* user_rows, const int64_t* nb_rows, const int64_t* it_off, const int64_t* keys, float* est) {
+        return nb_estimate_batch(h, family, measure, kind, n, user_rows, nb_offsets, nb_rows, it_off, keys, use_capper,
+                                 cap_min, cap_max, est);
+      });
 }
 
 // ---- the item-based recommenders over the set similarities (cms_set_item.hip) and over the co-rated ones

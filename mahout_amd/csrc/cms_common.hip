@@ -139,24 +139,29 @@ __global__ __launch_bounds__(kCommonPairThreads) void k_common_pairs(CommonSide 
 // ---- host side ----
 
 template <int MEASURE>
-static int launch_pairs_as(cms_handle* h, const CommonSide& v, const CommonPairArgs& g, int64_t total) {
+static int launch_pairs_as(cms_handle* h, const CommonSide& v, const CommonPairArgs& g, int64_t total,
+                           const char* scope) {
   const int64_t grid =
       std::min<int64_t>((total + kCommonPairThreads - 1) / kCommonPairThreads, (int64_t)h->num_cus * 32);
-  TimedScope ts(h, "common_pairs");
+  TimedScope ts(h, scope);
   hipLaunchKernelGGL(k_common_pairs<MEASURE>, dim3((unsigned)grid), dim3(kCommonPairThreads), 0, h->stream, v, g);
   CMS_HIP(hipGetLastError());
   return CMS_OK;
 }
 
-static int launch_pairs(cms_handle* h, int32_t measure, int32_t side, const CommonPairArgs& g) {
+int common_pairs_device(cms_handle* h, int32_t measure, int32_t side, const CommonPairArgs& g, const char* scope) {
   const int64_t total = g.cross ? g.n1 * g.n2 : g.n1;
   if (total <= 0) return CMS_OK;
   const CommonSide v = common_side(h, side);
   switch (measure) {
-    case kCommonUncentered: return launch_pairs_as<kCommonUncentered>(h, v, g, total);
-    case kCommonPearson: return launch_pairs_as<kCommonPearson>(h, v, g, total);
-    default: return launch_pairs_as<kCommonEuclidean>(h, v, g, total);
+    case kCommonUncentered: return launch_pairs_as<kCommonUncentered>(h, v, g, total, scope);
+    case kCommonPearson: return launch_pairs_as<kCommonPearson>(h, v, g, total, scope);
+    default: return launch_pairs_as<kCommonEuclidean>(h, v, g, total, scope);
   }
+}
+
+static int launch_pairs(cms_handle* h, int32_t measure, int32_t side, const CommonPairArgs& g) {
+  return common_pairs_device(h, measure, side, g, "common_pairs");
 }
 
 template <int MEASURE>

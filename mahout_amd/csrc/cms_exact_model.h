@@ -91,6 +91,12 @@ struct CommonPairArgs {
   int64_t ld;
 };
 
+// Device arrays in, device results out, queued on the handle's stream under the timing scope `scope`: the launch
+// inside common_pair_call (cms_common.hip) and set_pair_call (cms_set.hip), for a caller whose pairs and results
+// stay on the device (cms_neighbor.hip).  measure and side are validated by the caller.
+int common_pairs_device(cms_handle* h, int32_t measure, int32_t side, const CommonPairArgs& g, const char* scope);
+int set_pairs_device(cms_handle* h, int32_t measure, int32_t side, const CommonPairArgs& g, const char* scope);
+
 // The item-based estimate kernels' argument (k_set_item_estimate, k_common_item_estimate): one batch's preferences
 // and the plan of cms_set_item_plan.h.
 struct SetItemArgs {

@@ -235,6 +235,7 @@ struct Tunables {
   int set_tile = 0;         // CMS_SET_TILE: candidates per workgroup of k_set_tile, a multiple of 64 (0: kSetTileDefault)
   int set_est_tile = 0;     // CMS_SET_EST_TILE: items per workgroup of k_set_item_estimate, a multiple of 64 (0: the kind's default)
   int common_est_tile = 0;  // CMS_COMMON_EST_TILE: items per workgroup of k_common_item_estimate, a multiple of 64 (0: the default of the measure and kind)
+  int nb_est_tile = 0;      // CMS_NB_EST_TILE: candidate slots per workgroup of k_nb_estimate, a multiple of 64 (0: the kind's default)
 };
 struct ExactModel;  // the attached DataModel of the exact cosine (cms_exact.hip)
 }  // namespace cms
@@ -783,6 +784,13 @@ int set_item_estimate_batch(cms_handle* h, int32_t measure, int32_t kind, int64_
 int common_item_estimate_batch(cms_handle* h, int32_t measure, int32_t kind, int64_t n, const int64_t* pref_offsets,
                                const int64_t* pref_keys, const float* pref_vals, const int64_t* cand_offsets,
                                const int64_t* cand_keys, int32_t use_capper, float cap_min, float cap_max, float* out);
+// ---- cms_neighbor.hip: the user-based recommenders' estimates over a co-rated or a set similarity ----
+// exact_estimate_batch with userSimilarity the measure of family (CMS_FAMILY_*: CMS_SIM_* or CMS_SET_*) and the
+// estimate of kind (CMS_NB_*): GenericUserBasedRecommender's (generic) or GenericBooleanPrefUserBasedRecommender's
+// (boolean, the caps are not read).  family, measure and kind are validated by the caller.
+int nb_estimate_batch(cms_handle* h, int32_t family, int32_t measure, int32_t kind, int64_t n, const int64_t* user_rows,
+                      const int64_t* nb_offsets, const int64_t* nb_rows, const int64_t* item_offsets,
+                      const int64_t* item_keys, int32_t use_capper, float cap_min, float cap_max, float* out);
 // ---- cms_f64.hip (CMS_COUNTER_F64) ----
 int f64_ingest_csr(cms_handle* h, const int64_t* d_off, const int64_t* d_key, const float* d_val);
 int f64_ingest_coo_host(cms_handle* h, const int64_t* owner, const int64_t* key, const float* val, int64_t np);

@@ -26,6 +26,7 @@
 #define __dsub_rn(x, y) ((x) - (y))
 #define __dmul_rn(x, y) ((x) * (y))
 #define __ddiv_rn(x, y) ((x) / (y))
+#define __fadd_rn(x, y) ((x) + (y))
 #endif
 
 namespace cms {
@@ -238,6 +239,23 @@ struct BoolItemEstimate {
   CMS_HD float finish() const { return found ? (float)total : __builtin_nanf(""); }
 };
 
+// GenericBooleanPrefUserBasedRecommender.doEstimatePreference (:45-61) for one
+// candidate item: a FLOAT totalSimilarity from 0.0f, += (float) similarity (one
+// rounded fp32 addition) for every neighbour that is not the user and holds the
+// item, in neighbourhood order.  A NaN similarity is NOT skipped here (the
+// estimate is then NaN); no count rule, no capper; NaN when nobody holds it.
+struct BoolUserEstimate {
+  float total = 0.0f;
+  int found = 0;
+  CMS_HD void add(const double* sims, int64_t m) {
+    for (int64_t i = 0; i < m; ++i) {
+      found = 1;
+      total = __fadd_rn(total, (float)sims[i]);
+    }
+  }
+  CMS_HD float finish() const { return found ? total : __builtin_nanf(""); }
+};
+
 CMS_HD float item_estimate_one(const double* sims, const float* prefs, int64_t m, int use_capper, float lo, float hi) {
   ItemEstimate e;
   e.add(sims, prefs, m);
@@ -251,4 +269,5 @@ CMS_HD float item_estimate_one(const double* sims, const float* prefs, int64_t m
 #undef __dsub_rn
 #undef __dmul_rn
 #undef __ddiv_rn
+#undef __fadd_rn
 #endif

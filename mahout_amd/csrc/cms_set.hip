@@ -110,9 +110,9 @@ __global__ __launch_bounds__(kSetPairThreads) void k_set_pairs(CommonSide v, Com
 
 template <int MEASURE>
 static int launch_set_pairs_as(cms_handle* h, const CommonSide& v, const CommonPairArgs& g, int64_t total,
-                               int32_t owner_side) {
+                               int32_t owner_side, const char* scope) {
   const int64_t grid = std::min<int64_t>((total + kSetPairThreads - 1) / kSetPairThreads, (int64_t)h->num_cus * 32);
-  TimedScope ts(h, "set_pairs");
+  TimedScope ts(h, scope);
   hipLaunchKernelGGL(k_set_pairs<MEASURE>, dim3((unsigned)grid), dim3(kSetPairThreads), 0, h->stream, v, g, owner_side);
   CMS_HIP(hipGetLastError());
   return CMS_OK;
@@ -134,6 +134,19 @@ static int launch_set_tile_as(cms_handle* h, const CommonSide& v, const int64_t*
   return CMS_OK;
 }
 
+int set_pairs_device(cms_handle* h, int32_t measure, int32_t side, const CommonPairArgs& g, const char* scope) {
+  const int64_t total = g.cross ? g.n1 * g.n2 : g.n1;
+  if (total <= 0) return CMS_OK;
+  const CommonSide v = common_side(h, side);
+  const int32_t owner_side = side == CMS_SIDE_OWNER;
+  switch (measure) {
+    case kSetCooccurrence: return launch_set_pairs_as<kSetCooccurrence>(h, v, g, total, owner_side, scope);
+    case kSetTanimoto: return launch_set_pairs_as<kSetTanimoto>(h, v, g, total, owner_side, scope);
+    case kSetCityBlock: return launch_set_pairs_as<kSetCityBlock>(h, v, g, total, owner_side, scope);
+    default: return launch_set_pairs_as<kSetLogLikelihood>(h, v, g, total, owner_side, scope);
+  }
+}
+
 int set_pair_call(cms_handle* h, int32_t measure, int32_t side, const int64_t* i1, int64_t n1, const int64_t* i2,
                   int64_t n2, bool cross, double* out) {
   ExactModel& m = *h->exact;
@@ -143,15 +156,7 @@ int set_pair_call(cms_handle* h, int32_t measure, int32_t side, const int64_t* i
   if ((rc = upload(h, m.q1, i1, (size_t)n1)) || (rc = upload(h, m.q2, i2, (size_t)n2))) return rc;
   CMS_HIP(m.out.ensure(sizeof(double) * (size_t)total));
   const CommonPairArgs g{m.q1.as<int64_t>(), m.q2.as<int64_t>(), nullptr, n1, n2, cross ? 1 : 0, 0, m.out.as<double>(), n2};
-  const CommonSide v = common_side(h, side);
-  const int32_t owner_side = side == CMS_SIDE_OWNER;
-  switch (measure) {
-    case kSetCooccurrence: rc = launch_set_pairs_as<kSetCooccurrence>(h, v, g, total, owner_side); break;
-    case kSetTanimoto: rc = launch_set_pairs_as<kSetTanimoto>(h, v, g, total, owner_side); break;
-    case kSetCityBlock: rc = launch_set_pairs_as<kSetCityBlock>(h, v, g, total, owner_side); break;
-    default: rc = launch_set_pairs_as<kSetLogLikelihood>(h, v, g, total, owner_side); break;
-  }
-  if (rc) return rc;
+  if ((rc = set_pairs_device(h, measure, side, g, "set_pairs"))) return rc;
   CMS_HIP(hipMemcpyAsync(out, m.out.ptr, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, h->stream));
   CMS_HIP(hipStreamSynchronize(h->stream));
   return CMS_OK;

@@ -634,6 +634,76 @@ class SketchTable:
                                           self._common_args(measure, "key")[0], kind, user_ids, how_many, strategy,
                                           include_known, capper)
 
+    # -- user-based recommenders over the co-rated and the set similarities --
+    NB_KINDS = {"generic": 0, "boolean": 1}  # CMS_NB_*
+
+    @classmethod
+    def _neighbor_args(cls, measure, kind):
+        """(family, measure, kind) as the C values.  The family is taken from
+        the measure's name (the two name sets are disjoint); measure may also
+        be the pair (family, measure) of C values, an unknown one being the
+        library's CMS_E_PARAM."""
+        if isinstance(measure, str):
+            if measure in cls.COMMON_MEASURES:
+                fam, ms = 0, cls.COMMON_MEASURES[measure]
+            elif measure in cls.SET_MEASURES:
+                fam, ms = 1, cls.SET_MEASURES[measure]
+            else:
+                raise ValueError(f"unknown measure {measure!r}")
+        else:
+            fam, ms = measure
+        return int(fam), int(ms), int(cls.NB_KINDS.get(kind, kind))
+
+    def neighbor_estimate_preferences(self, user_id, neighbor_ids, item_keys, measure="pearson", kind="generic",
+                                      capper=None):
+        """doEstimatePreference(user, neighbourhood, item) for every item key
+        over the attached model with userSimilarity the named measure of the
+        co-rated or the set family: GenericUserBasedRecommender's estimate
+        (kind="generic") or GenericBooleanPrefUserBasedRecommender's
+        (kind="boolean", no capper).  A batch of one user."""
+        nb = np.ascontiguousarray(neighbor_ids, np.int64).reshape(-1)
+        it = np.ascontiguousarray(item_keys, np.int64).reshape(-1)
+        return self.neighbor_estimate_preferences_batch([user_id], [0, nb.size], nb, [0, it.size], it, measure, kind,
+                                                        capper)
+
+    def neighbor_estimate_preferences_batch(self, user_ids, nb_offsets, neighbor_ids, item_offsets, item_keys,
+                                            measure="pearson", kind="generic", capper=None):
+        """neighbor_estimate_preferences for many users in one call
+        (cms_neighbor_estimate_preferences_batch), shaped as
+        exact_estimate_preferences_batch."""
+        us, nbo, nb, ito, it = SketchTable._estimate_batch_args(user_ids, nb_offsets, neighbor_ids, item_offsets,
+                                                                item_keys)
+        fam, ms, kd = self._neighbor_args(measure, kind)
+        out = np.zeros(it.size, np.float32)
+        lo, hi = capper if capper is not None else (0.0, 0.0)
+        check(self._lib.cms_neighbor_estimate_preferences_batch(self._h, fam, ms, kd, us.size, _ptr(us), _ptr(nbo),
+                                                                _ptr(nb), _ptr(ito), _ptr(it), int(capper is not None),
+                                                                float(lo), float(hi), _ptr(out)))
+        return out
+
+    def neighbor_recommend_batch(self, user_ids, nb_offsets, neighbor_ids, how_many, measure="pearson", kind="generic",
+                                 include_known=False, capper=None):
+        """cms_neighbor_recommend_batch: recommend() of the user-based
+        recommender of `kind` over neighbor_estimate_preferences for every
+        user of user_ids at once, shaped as exact_recommend_batch.  Returns
+        (counts [n], items [n][how_many], values [n][how_many] float32)."""
+        us = np.ascontiguousarray(user_ids, np.int64).reshape(-1)
+        nbo = np.ascontiguousarray(nb_offsets, np.int64).reshape(-1)
+        nb = np.ascontiguousarray(neighbor_ids, np.int64).reshape(-1)
+        if nbo.size != us.size + 1 or nbo[0] != 0 or nbo[-1] != nb.size or bool(np.any(np.diff(nbo) < 0)):
+            raise ValueError("nb_offsets must hold len(user_ids) + 1 non-decreasing entries from 0 to len(neighbor_ids)")
+        if how_many < 1:
+            raise ValueError("howMany must be at least 1")
+        fam, ms, kd = self._neighbor_args(measure, kind)
+        counts = np.zeros(us.size, np.int32)
+        items = np.full((us.size, how_many), -1, np.int64)
+        vals = np.full((us.size, how_many), np.nan, np.float32)
+        lo, hi = capper if capper is not None else (0.0, 0.0)
+        check(self._lib.cms_neighbor_recommend_batch(self._h, fam, ms, kd, us.size, _ptr(us), _ptr(nbo), _ptr(nb),
+                                                     int(how_many), int(bool(include_known)), int(capper is not None),
+                                                     float(lo), float(hi), _ptr(counts), _ptr(items), _ptr(vals)))
+        return counts, items, vals
+
     # -- anonymous profiles: preferences that are no row of the table --
     @staticmethod
     def _profile(keys, vals):

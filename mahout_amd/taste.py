@@ -577,9 +577,10 @@ class _CommonSimilarity(CosineSimilarity):
     NaN.  The handle, refresh and close are CosineSimilarity's.
 
     The neighbourhoods are served (nearestNeighborhoods, so
-    NearestNUserNeighborhood works unchanged); the device estimate and batch
-    recommend of GenericUserBasedRecommender are not: the library's estimate
-    batch forms its similarities with the full-norm cosine."""
+    NearestNUserNeighborhood works unchanged), and the user-based recommenders'
+    estimates and batch recommend through userEstimatesBatch /
+    userRecommendBatch, which take the recommender's kind; estimatePreferences
+    and recommendBatch, which have no kind to go by, refuse."""
 
     MEASURE = None
 
@@ -631,6 +632,20 @@ class _CommonSimilarity(CosineSimilarity):
 
     def recommendBatch(self, userIDs, nb_offsets, neighborIDs, modelCSR, howMany, includeKnownItems=False, capper=None):
         raise NotImplementedError("the device batch recommend takes its similarities from the full-norm cosine only")
+
+    # the user-based recommenders' device route (GenericUserBasedRecommender looks for these two): the
+    # estimate's kind is the recommender's, which is why estimatePreferences alone cannot answer
+    def userEstimatesBatch(self, kind, userIDs, nb_offsets, neighborIDs, item_offsets, itemIDs, capper=None):
+        """doEstimatePreference of the user-based recommender of `kind` ("generic", "boolean") for many
+        users in one device batch, this measure scoring the neighbours (cms_neighbor_estimate_preferences_batch)."""
+        return self._table.neighbor_estimate_preferences_batch(userIDs, nb_offsets, neighborIDs, item_offsets, itemIDs,
+                                                               self.MEASURE, kind, capper)
+
+    def userRecommendBatch(self, kind, userIDs, nb_offsets, neighborIDs, howMany, includeKnownItems=False, capper=None):
+        """recommend for many users (cms_neighbor_recommend_batch), the attached model as the DataModel:
+        (counts, items, values)."""
+        return self._table.neighbor_recommend_batch(userIDs, nb_offsets, neighborIDs, howMany, self.MEASURE, kind,
+                                                    includeKnownItems, capper)
 
     # the item-based recommenders' device route (GenericItemBasedRecommender looks for these three)
     def servesItemModel(self, dataModel):
@@ -832,7 +847,12 @@ class GenericUserBasedRecommender:
     CosineSimilarity the one over the DataModel's own values (sim == null),
     capped by EstimatedPreferenceCapper when the model has min/max (:209-216).
     The similarity serves the neighbourhoods, the estimates and the batch
-    recommend (nearestNeighborhoods, estimatePreferences, recommendBatch)."""
+    recommend (nearestNeighborhoods, estimatePreferences, recommendBatch).
+    A co-rated or a set similarity (Pearson, Tanimoto, ...) serves the last two
+    through userEstimatesBatch / userRecommendBatch, which take the estimate's
+    kind from the recommender class (KIND)."""
+
+    KIND = "generic"
 
     def __init__(self, dataModel, neighborhood, similarity):
         self._model = dataModel
@@ -854,6 +874,9 @@ class GenericUserBasedRecommender:
         if theUserID == PlusAnonymousUserDataModel.TEMP_USER_ID and isinstance(self._model, PlusAnonymousUserDataModel):
             return self._sim.anonymousEstimates(theNeighborhood, itemIDs, self._capper)
         try:
+            if hasattr(self._sim, "userEstimatesBatch"):
+                return self._sim.userEstimatesBatch(self.KIND, [theUserID], [0, len(theNeighborhood)], theNeighborhood,
+                                                    [0, len(itemIDs)], itemIDs, self._capper)
             return self._sim.estimatePreferences(theUserID, theNeighborhood, itemIDs, self._capper)
         except _lib.CmsError as e:
             raise _map_error(e, "user")
@@ -903,8 +926,12 @@ class GenericUserBasedRecommender:
         users = np.ascontiguousarray(userIDs, np.int64)
         nb_off, nb = self._nb.getUserNeighborhoods(users)
         try:
-            cnt, items, vals = self._sim.recommendBatch(users, nb_off, nb, self._model_csr(), howMany,
-                                                        includeKnownItems, self._capper)
+            if hasattr(self._sim, "userRecommendBatch"):
+                cnt, items, vals = self._sim.userRecommendBatch(self.KIND, users, nb_off, nb, howMany, includeKnownItems,
+                                                                self._capper)
+            else:
+                cnt, items, vals = self._sim.recommendBatch(users, nb_off, nb, self._model_csr(), howMany,
+                                                            includeKnownItems, self._capper)
         except _lib.CmsError as e:
             raise _map_error(e, "user")
         return [[(int(items[u, j]), vals[u, j]) for j in range(int(cnt[u]))] for u in range(users.size)]
@@ -924,6 +951,27 @@ class GenericUserBasedRecommender:
         items = self.getAllOtherItems(nb, userID, includeKnownItems).toList()
         est = self.doEstimatePreferences(userID, nb, items) if items else np.zeros(0, np.float32)
         return get_top_items(howMany, items, est)
+
+
+class GenericBooleanPrefUserBasedRecommender(GenericUserBasedRecommender):
+    """GenericBooleanPrefUserBasedRecommender(model, neighborhood, similarity)
+    (T/impl/recommender/GenericBooleanPrefUserBasedRecommender.java): the
+    user-based recommender for data without preference values.  Its estimate
+    (:45-61) is the float sum of the similarities of the neighbours that hold
+    the item -- no preference value, no count rule, no capper, a NaN
+    similarity not skipped; the neighbourhood, the candidates and the ranking
+    are GenericUserBasedRecommender's.  The similarity must serve the
+    user-based device route (a Tanimoto, log-likelihood, city-block or a
+    co-rated similarity)."""
+
+    KIND = "boolean"
+
+    def __init__(self, dataModel, neighborhood, similarity):
+        if not (hasattr(similarity, "userEstimatesBatch") and hasattr(similarity, "userRecommendBatch")):
+            raise NotImplementedError(f"{type(similarity).__name__} does not serve the boolean user-based estimate "
+                                      "(userEstimatesBatch / userRecommendBatch)")
+        super().__init__(dataModel, neighborhood, similarity)
+        self._capper = None
 
 
 # ---- the item-based recommender ------------------------------------------------
