@@ -949,6 +949,24 @@ int cms_set_pairs(cms_handle* h, int32_t measure, int32_t side, const int64_t* i
  * cms_common_top_k.  Timing scopes "set_tile", "top_k". */
 int cms_set_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* ids, int64_t nq, int32_t k,
                   int64_t* out_ids, double* out_scores, int32_t* out_counts);
+/* cms_set_top_k for every list of the side in list order -- the owners in
+ * owner-row order (CMS_SIDE_OWNER), the attached keys ascending (CMS_SIDE_KEY)
+ * -- so out_ids / out_scores are [lists][k] and out_counts [lists], laid out,
+ * ordered and padded as cms_set_top_k over those IDs, with the same bits.  The
+ * shared-entry counts come from a bit matrix of the side on the matrix units
+ * (built by the first call that needs it, dropped by the next attach) when it
+ * fits CMS_SET_BITS_MB MiB (environment, read at cms_create; default 16384,
+ * 0: never), else from cms_set_top_k's kernel; the call never fails for the
+ * matrix's size.  Timing scopes "set_bits_pack", "set_bits_mfma", "top_k"
+ * (without a matrix: "set_tile", "top_k"). */
+int cms_set_top_k_all(cms_handle* h, int32_t measure, int32_t side, int32_t k, int64_t* out_ids, double* out_scores,
+                      int32_t* out_counts);
+/* The dense block out[i * n2 + j] = similarity(ids1[i], ids2[j]), the bits of
+ * cms_set_similarities(h, measure, side, ids1[i], &ids2[j], 1, ...); IDs may
+ * repeat and come in any order.  Routed as cms_set_top_k_all ("set_bits_mfma",
+ * without a matrix "set_pairs"). */
+int cms_set_block(cms_handle* h, int32_t measure, int32_t side, const int64_t* ids1, int64_t n1, const int64_t* ids2,
+                  int64_t n2, double* out);
 
 /* ---- user-based recommenders over the co-rated and the set similarities -----
  * cms_exact_estimate_preferences_batch and cms_exact_recommend_batch with

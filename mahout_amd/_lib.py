@@ -60,7 +60,7 @@ EXPORTS = [
     "cms_exact_most_similar", "cms_owner_rows",
     "cms_exact_estimate_preferences_batch", "cms_exact_recommend_batch",
     "cms_common_similarities", "cms_common_pairs", "cms_common_top_k",
-    "cms_set_similarities", "cms_set_pairs", "cms_set_top_k",
+    "cms_set_similarities", "cms_set_pairs", "cms_set_top_k", "cms_set_top_k_all", "cms_set_block",
     "cms_set_item_estimates_batch", "cms_set_item_recommend_batch",
     "cms_common_item_estimates_batch", "cms_common_item_recommend_batch",
     "cms_neighbor_estimate_preferences_batch", "cms_neighbor_recommend_batch",
@@ -228,6 +228,8 @@ _SIGS = {
     "cms_set_similarities": (_int, [_vp, _i32, _i32, _i64, _vp, _i64, _vp]),
     "cms_set_pairs": (_int, [_vp, _i32, _i32, _vp, _vp, _i64, _vp]),
     "cms_set_top_k": (_int, [_vp, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "cms_set_top_k_all": (_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "cms_set_block": (_int, [_vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp]),
     "cms_set_item_estimates_batch": (_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_float,
                                             ctypes.c_float, _vp]),
     "cms_set_item_recommend_batch": (_int, [_vp, _i32, _i32, _i64, _vp, _i32, _i32, _i32, _i32, ctypes.c_float,

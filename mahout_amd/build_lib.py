@@ -9,13 +9,13 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmahout_cms.so")
 SOURCES = ["cms_api.hip", "cms_ingest.hip", "cms_build.hip", "cms_partition.hip", "cms_query.hip", "cms_topk.hip", "cms_cosine_mfma.hip", "cms_cosine_sym.hip", "cms_cosine_mls.hip", "cms_profiles.hip", "cms_merge.hip", "cms_table.hip", "cms_f64.hip", "cms_output.cpp", "cms_recommend.cpp",
            "cms_checkpoint.hip", "cms_checkpoint.cpp", "cms_anonymous.hip", "cms_retract.hip", "cms_fold.hip", "cms_threshold.hip", "cms_item.hip", "cms_exact.hip", "cms_common.hip", "cms_set.hip", "cms_set_item.hip",
-           "cms_common_item.hip", "cms_neighbor.hip"]
+           "cms_common_item.hip", "cms_neighbor.hip", "cms_set_bits.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
          "-mcode-object-version=5", "-Wall", "-Wno-unused-function", "-I/opt/rocm/include"]
 # per-file additions: no packed fp32 operations in the co-rated and the set similarities' kernels
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"cms_common.hip": NO_PACKED_FP32, "cms_set.hip": NO_PACKED_FP32, "cms_set_item.hip": NO_PACKED_FP32,
-              "cms_common_item.hip": NO_PACKED_FP32}
+              "cms_common_item.hip": NO_PACKED_FP32, "cms_set_bits.hip": NO_PACKED_FP32}
 
 
 def build(verbose=False, force=False, jobs=None, defines=(), out=None):

@@ -362,6 +362,8 @@ static int create_impl(const cms_params* p, bool per_owner, cms_handle** out) {
     h->tune.exact_est_tile = std::max(0, num("CMS_EXACT_EST_TILE", 0));
     h->tune.common_tile = std::max(0, num("CMS_COMMON_TILE", 0));
     h->tune.set_tile = std::max(0, num("CMS_SET_TILE", 0));
+    h->tune.set_bits_mb = std::max(0, num("CMS_SET_BITS_MB", (int)h->tune.set_bits_mb));
+    h->tune.set_bits_kseg = std::max(0, num("CMS_SET_BITS_KSEG", 0));
     h->tune.set_est_tile = std::max(0, num("CMS_SET_EST_TILE", 0));
     h->tune.common_est_tile = std::max(0, num("CMS_COMMON_EST_TILE", 0));
     h->tune.nb_est_tile = std::max(0, num("CMS_NB_EST_TILE", 0));
@@ -2020,6 +2022,44 @@ int cms_set_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* i
   CMS_HIP(hipMemcpyAsync(out_counts, o_cnt.ptr, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
   CMS_HIP(hipStreamSynchronize(h->stream));
   return CMS_OK;
+}
+
+int cms_set_top_k_all(cms_handle* h, int32_t measure, int32_t side, int32_t k, int64_t* out_ids, double* out_scores,
+                      int32_t* out_counts) {
+  if (!h || !out_ids || !out_counts) return set_error(CMS_E_PARAM, "null argument");
+  if (k < 1 || k > kCandCap / 2) return set_error(CMS_E_PARAM, "k must be in [1, %d]", kCandCap / 2);
+  Guard g(h);
+  int rc = set_require(h, "cms_set_top_k_all", measure, side);
+  if (rc) return rc;
+  const int64_t nq = set_side_lists(h, side);
+  if (nq == 0) return CMS_OK;
+  DevBuf o_ids, o_sc, o_cnt;
+  const size_t cells = (size_t)nq * (size_t)k;
+  CMS_HIP(o_ids.ensure(sizeof(int64_t) * cells));
+  CMS_HIP(o_sc.ensure(sizeof(double) * cells));
+  CMS_HIP(o_cnt.ensure(sizeof(int32_t) * (size_t)nq));
+  CMS_HIP(hipMemsetAsync(o_ids.ptr, 0xFF, sizeof(int64_t) * cells, h->stream));  // padding: ID -1, all-ones NaN
+  CMS_HIP(hipMemsetAsync(o_sc.ptr, 0xFF, sizeof(double) * cells, h->stream));
+  CMS_HIP(hipMemsetAsync(o_cnt.ptr, 0, sizeof(int32_t) * (size_t)nq, h->stream));
+  if ((rc = set_bits_top_k_all(h, measure, side, k, o_ids.as<int64_t>(), o_sc.as<double>(), o_cnt.as<int32_t>())))
+    return rc;
+  CMS_HIP(hipMemcpyAsync(out_ids, o_ids.ptr, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, h->stream));
+  if (out_scores) CMS_HIP(hipMemcpyAsync(out_scores, o_sc.ptr, sizeof(double) * cells, hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipMemcpyAsync(out_counts, o_cnt.ptr, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
+  CMS_HIP(hipStreamSynchronize(h->stream));
+  return CMS_OK;
+}
+
+int cms_set_block(cms_handle* h, int32_t measure, int32_t side, const int64_t* ids1, int64_t n1, const int64_t* ids2,
+                  int64_t n2, double* out) {
+  if (!h || n1 < 0 || n2 < 0 || (n1 > 0 && !ids1) || (n2 > 0 && !ids2) || (n1 > 0 && n2 > 0 && !out))
+    return set_error(CMS_E_PARAM, "null argument");
+  Guard g(h);
+  int rc = set_require(h, "cms_set_block", measure, side);
+  if (rc) return rc;
+  std::vector<int64_t> i1, i2;
+  if ((rc = common_indices(h, side, ids1, n1, i1)) || (rc = common_indices(h, side, ids2, n2, i2))) return rc;
+  return set_bits_block(h, measure, side, i1.data(), n1, i2.data(), n2, out);
 }
 
 // ---- the user-based recommenders over the co-rated and the set similarities (cms_neighbor.hip) ----

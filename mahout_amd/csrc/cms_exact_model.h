@@ -35,6 +35,10 @@ struct ExactModel {
   std::vector<uint8_t> h_cseq[2];  // [n], [nitems]
   DevBuf cseq[2];                  // i64 indices, ascending
   int64_t n_cseq[2] = {0, 0};
+  // the dense route of the set similarities (cms_set_bits.hip): per side (owner, key) the bit matrix, built by the
+  // first call that needs it and gone with the model.  state 0: not tried, 1: built, -1: no room (budget or memory)
+  DevBuf bits[2];
+  int bits_state[2] = {0, 0};
 };
 
 // (the host array must stay alive until the stream is synchronised)

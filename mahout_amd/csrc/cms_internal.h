@@ -233,6 +233,8 @@ struct Tunables {
   int exact_est_tile = 0;   // CMS_EXACT_EST_TILE: candidate slots per workgroup of k_exact_estimate, a multiple of 64 (0: kExactEstTile)
   int common_tile = 0;      // CMS_COMMON_TILE: candidates per workgroup of k_common_tile, a multiple of 64 (0: the measure's default)
   int set_tile = 0;         // CMS_SET_TILE: candidates per workgroup of k_set_tile, a multiple of 64 (0: kSetTileDefault)
+  int64_t set_bits_mb = 16384;  // CMS_SET_BITS_MB: MiB a side's bit matrix may take (cms_set_bits.hip; 0: never built)
+  int64_t set_bits_kseg = 0;    // CMS_SET_BITS_KSEG: cross indices per f32 segment of k_set_bits_mfma, whole stages (0: 2^24)
   int set_est_tile = 0;     // CMS_SET_EST_TILE: items per workgroup of k_set_item_estimate, a multiple of 64 (0: the kind's default)
   int common_est_tile = 0;  // CMS_COMMON_EST_TILE: items per workgroup of k_common_item_estimate, a multiple of 64 (0: the default of the measure and kind)
   int nb_est_tile = 0;      // CMS_NB_EST_TILE: candidate slots per workgroup of k_nb_estimate, a multiple of 64 (0: the kind's default)
@@ -768,6 +770,17 @@ int set_pair_call(cms_handle* h, int32_t measure, int32_t side, const int64_t* i
                   int64_t n2, bool cross, double* out);
 int set_top_k(cms_handle* h, int32_t measure, int32_t side, const int64_t* idx, int64_t nq, int32_t k, int64_t* d_ids,
               double* d_scores, int32_t* d_counts);
+// ---- cms_set_bits.hip: the set similarities of many lists against many on the matrix units ----
+// (h->exact is non-null; measure and side are validated by the caller.)  Both answer from the side's bit matrix
+// (k_set_bits_mfma) when CMS_SET_BITS_MB has room for it, else through set_top_k and set_pair_call, with the same bits.
+// the lists of a side: the owner rows, or the attached model's distinct keys
+int64_t set_side_lists(const cms_handle* h, int32_t side);
+// the k most similar lists of every list of the side, in list order, into device outputs laid out as set_top_k's
+int set_bits_top_k_all(cms_handle* h, int32_t measure, int32_t side, int32_t k, int64_t* d_ids, double* d_scores,
+                       int32_t* d_counts);
+// host indices in, host results out (blocking): out[i * n2 + j] = similarity(i1[i], i2[j])
+int set_bits_block(cms_handle* h, int32_t measure, int32_t side, const int64_t* i1, int64_t n1, const int64_t* i2,
+                   int64_t n2, double* out);
 // ---- cms_set_item.hip: the item-based recommenders' estimates over the set similarities ----
 // (h->exact is non-null; measure and kind are validated by the caller: CMS_SET_*, CMS_ITEM_EST_*)
 // doEstimatePreference of GenericItemBasedRecommender (weighted) or GenericBooleanPrefItemBasedRecommender

@@ -374,6 +374,8 @@ class SketchTable:
         if keys.size != vals.size or (offsets.size and int(offsets.max()) > keys.size):
             raise ValueError("offsets reach past the keys, or keys and vals differ in length")
         check(self._lib.cms_exact_attach_csr(self._h, _ptr(offsets), _ptr(keys), _ptr(vals)))
+        self._attached_keys = keys[:int(offsets[-1])]  # set_top_k_all sizes the key side's output from them
+        self._attached_nkeys = None
 
     def owner_rows(self, owner_ids):
         """The owner rows of owner IDs (cms_owner_rows; CMS_E_NO_SUCH_ID for an unknown one)."""
@@ -384,6 +386,7 @@ class SketchTable:
 
     def detach_exact(self):
         check(self._lib.cms_exact_detach(self._h))
+        self._attached_keys = self._attached_nkeys = None
 
     def exact_similarities(self, id1, ids2):
         """CosineSimilarity.userSimilarity(id1, ids2[t]) over the attached model."""
@@ -511,6 +514,7 @@ class SketchTable:
 
     # -- the set similarities over the attached DataModel --
     SET_MEASURES = {"cooccurrence": 0, "tanimoto": 1, "city_block": 2, "loglikelihood": 3}  # CMS_SET_*
+    _attached_keys = _attached_nkeys = None  # the attached model's keys (attach_exact) and how many are distinct
 
     def attach_sets(self, offsets, keys=None, vals=None):
         """The owners' DataModel for the set similarities: a CSR over the
@@ -562,6 +566,33 @@ class SketchTable:
         ms, sd = self._set_args(measure, side)
         check(self._lib.cms_set_top_k(self._h, ms, sd, _ptr(ids), ids.size, int(k), _ptr(out), _ptr(sc), _ptr(cnt)))
         return out, sc, cnt
+
+    def set_top_k_all(self, k, measure="loglikelihood", side="owner"):
+        """set_top_k for every list of the side in list order -- the owners in
+        row order, or the attached keys ascending -- in one job
+        (cms_set_top_k_all): (ids [lists][k], scores, counts), the bits of
+        set_top_k over those IDs.  The shared-entry counts come from the side's
+        bit matrix on the matrix units while it fits CMS_SET_BITS_MB."""
+        ms, sd = self._set_args(measure, side)
+        if sd != 0 and self._attached_keys is not None and self._attached_nkeys is None:
+            self._attached_nkeys = int(np.unique(self._attached_keys).size)  # once per attached model
+        n = self.num_owners if sd == 0 or self._attached_nkeys is None else self._attached_nkeys
+        out = np.zeros((n, k), np.int64)
+        sc = np.zeros((n, k), np.float64)
+        cnt = np.zeros(n, np.int32)
+        check(self._lib.cms_set_top_k_all(self._h, ms, sd, int(k), _ptr(out), _ptr(sc), _ptr(cnt)))
+        return out, sc, cnt
+
+    def set_similarity_block(self, ids1, ids2, measure="loglikelihood", side="owner"):
+        """The dense block similarity(ids1[i], ids2[j]) as float64 [n1][n2]
+        (cms_set_block): row i holds the bits of set_similarities(ids1[i],
+        ids2).  IDs may repeat and come in any order."""
+        ids1 = np.ascontiguousarray(ids1, np.int64).reshape(-1)
+        ids2 = np.ascontiguousarray(ids2, np.int64).reshape(-1)
+        out = np.zeros((ids1.size, ids2.size), np.float64)
+        ms, sd = self._set_args(measure, side)
+        check(self._lib.cms_set_block(self._h, ms, sd, _ptr(ids1), ids1.size, _ptr(ids2), ids2.size, _ptr(out)))
+        return out
 
     # -- item-based recommenders over the set similarities --
     ITEM_EST_KINDS = {"weighted": 0, "boolean": 1}  # CMS_ITEM_EST_*

@@ -721,6 +721,31 @@ class _SetSimilarity(_CommonSimilarity):
         except _lib.CmsError as e:
             raise _map_error(e, "user")
 
+    # every list's most similar lists in one device job, and dense blocks (cms_set_top_k_all, cms_set_block)
+    def _top_all(self, howMany, side, kind):
+        if howMany < 1:
+            raise ValueError("howMany must be at least 1")
+        try:
+            return self._table.set_top_k_all(howMany, self.MEASURE, side)
+        except _lib.CmsError as e:
+            raise _map_error(e, kind)
+
+    def allMostSimilarItemIDs(self, howMany):
+        """mostSimilarItems of every item of the model, the batch MultithreadedBatchItemSimilarities runs item by
+        item: (itemIDs, ids [items][howMany], scores, counts), itemIDs ascending, a row padded with -1 / NaN."""
+        return (np.asarray(self._model.getItemIDs(), np.int64), *self._top_all(howMany, "key", "item"))
+
+    def allMostSimilarUserIDs(self, howMany):
+        """mostSimilarUserIDs of every user, in getUserIDs() order: (userIDs, ids, scores, counts)."""
+        return (np.asarray(self._model.getUserIDs(), np.int64), *self._top_all(howMany, "owner", "user"))
+
+    def itemSimilarityBlock(self, itemIDs1, itemIDs2):
+        """itemSimilarity(itemIDs1[i], itemIDs2[j]) as float64 [n1][n2], the bits of itemSimilarities row by row."""
+        try:
+            return self._table.set_similarity_block(itemIDs1, itemIDs2, self.MEASURE, "key")
+        except _lib.CmsError as e:
+            raise _map_error(e, "item")
+
     def estimatePreferences(self, theUserID, theNeighborhood, itemIDs, capper=None):
         raise NotImplementedError("the boolean recommenders' estimates are not served on the device")
 
